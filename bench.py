@@ -1,17 +1,19 @@
 """Headline benchmark: attention forward (and forward+backward) TFLOP/s on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows 5] [--preroll-ms 400] [--no-sweep] [--no-cpu] [--no-traffic] [--no-parity]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--windows 1] [--preroll-ms 400] [--dump-outputs DIR]
+                    [--full [--no-sweep] [--no-cpu] [--no-traffic] [--no-parity]]
 
 Workload (BASELINE.json): config 3 -- B=4 H=32 S=4096 D=128 bf16 causal, synthetic N(0,1) inputs
-resident in HBM.  One "step" = one forward pass of the hot path (fa_fwd through the C ABI); the
+resident in HBM.  One "step" = one forward pass of the hot path (fa_fwd through the C ABI).  A plain run measures that and nothing
+else; `--dump-outputs DIR` then writes what the last timed step returned (see dump_outputs).  Only with `--full`: the
 forward+backward rate on the same config, the reference's seqlen sweep (S = 512 .. 16k at D = 128 and D = 64, causal and not), BASELINE's
 configs 2 / 4 / 5 at their real shapes (`configs`) and the error table of the timed workload against PyTorch fp32 / bf16 / an fp64 sample
 (`parity`, default and FA_STRICT numerics) and the opt-in fused backward next to the default one (`bwd_fused`, timed in a child process under a timeout) are reported as extra keys, `roofline.kernel` is what fa_last_schedule() says the C ABI launched, `roofline.traffic` comes from
 two rocprofv3 --pmc passes run from here (outside the timed region).  FLOP convention = the reference's (benchmarks/benchmark_flash_attention.py:
 27-30): fwd = 4*B*H*S^2*D (/2 causal), bwd = 2.5x, fwd+bwd = 3.5x.
-Timing: an untimed clock ramp (>= --preroll-ms of the same launch), W counted warm-up launches, then --windows regions of EXACTLY K
-launches each, every region bracketed by barrier + synchronize; `ms_per_step` / `value` come from the median region (max over ranks),
-min / max are kept under `windows`.
+Timing: an untimed clock ramp (>= --preroll-ms of the same launch), W counted warm-up launches, then --windows regions (default one, so
+that K is the number of timed steps) of EXACTLY K launches each, every region bracketed by barrier + synchronize; `ms_per_step` /
+`value` come from the median region (max over ranks), min / max are kept under `windows`.
 N>1: independent replicas, one process per GPU (the path has no exchange step): under a launcher (WORLD_SIZE set) this
 process is one rank; without one, `--gpus N` starts the N ranks itself.
 """
@@ -53,9 +55,10 @@ def time_kernel(fn, steps, warmup, sync):
 def cpu_baseline(D, S, causal, heads=8, reps=2):
     """Reference CPU SDPA (torch F.scaled_dot_product_attention, bf16) on a bounded sample of the same
     workload: `heads` (batch, head) units of config 3 (units are independent, so the rate is per-unit
-    exact); all host cores.  Forward, and forward+backward through autograd (one rep)."""
+    exact); all host cores, or OMP_NUM_THREADS of them where the environment limits the process so.  Forward, and forward+backward
+    through autograd (one rep)."""
     import torch.nn.functional as F
-    n = os.cpu_count() or 1
+    n = int(os.environ.get("OMP_NUM_THREADS", "").split(",")[0] or 0) or os.cpu_count() or 1
     torch.set_num_threads(n)
     g = torch.Generator().manual_seed(0)
     q = torch.randn(1, heads, S, D, generator=g).bfloat16()
@@ -477,6 +480,18 @@ def timed_windows(fn, steps, windows, sync, world, dev, use_events=True):
     return out
 
 
+def dump_outputs(d, out, lse, rows=512, seed=0):
+    """`--dump-outputs DIR`: what the timed path returned in its last timed step, in float32 -- `lse.npy` (B, H, S) whole, and `out.npy`
+    (B, rows, H, D): `out` at a fixed sample of `rows` query positions (drawn with `seed`, in ascending order), 34 MiB in all at config 3
+    where the whole of `out` would be 64 MiB.  The inputs are seeded, so the same arguments give the same files on the same build."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    S = out.shape[1]
+    idx = torch.randperm(S, generator=torch.Generator().manual_seed(seed))[:min(rows, S)].sort().values
+    np.save(os.path.join(d, "out.npy"), out[:, idx.to(out.device)].float().cpu().numpy())
+    np.save(os.path.join(d, "lse.npy"), lse.float().cpu().numpy())
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -495,8 +510,12 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps launches; ms_per_step / value = the median window")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps launches; ms_per_step / value = the median window")
     ap.add_argument("--preroll-ms", type=float, default=400.0, help="clock ramp before the counted warm-up (same launch, untimed)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: fwd+bwd, PMC traffic, sweeps, configs, features, fused-backward probe, "
+                         "parity, CPU baseline (each still subject to its --no-* switch)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the seqlen sweep (extra key `sweep`)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the error table of the timed workload (extra key `parity`)")
@@ -505,7 +524,10 @@ def parse_args(argv=None):
     ap.add_argument("--fused-probe", action="store_true", help="(internal) time the opt-in fused backward next to the default one and print the rows as JSON")
     ap.add_argument("--stub-workload", action="store_true",
                     help="(tests only) CPU + gloo run of the launcher / timing / aggregation code with a sleep in place of the kernel; the line says so")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.dump_outputs and a.stub_workload:
+        ap.error("--dump-outputs needs the real workload: no kernel runs under --stub-workload")
+    return a
 
 
 def main(argv=None):
@@ -546,7 +568,11 @@ def main(argv=None):
         q = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
         k = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
         v = torch.randn(B, S, H, D, device=dev, dtype=torch.bfloat16)
-        fwd = lambda: be.fwd(q, k, v, None, None, 0.0, scale, causal, -1, -1, 0.0, False, None)
+        last = [None]   # what the latest step returned: after the timed windows, the last timed step's outputs (--dump-outputs)
+
+        def fwd():
+            last[0] = be.fwd(q, k, v, None, None, 0.0, scale, causal, -1, -1, 0.0, False, None)
+            return last[0]
         dev_sync = lambda: torch.cuda.synchronize(dev)
     dist_on = world > 1
     if dist_on:
@@ -580,16 +606,21 @@ def main(argv=None):
             dist.destroy_process_group()
         return
 
-    # forward + backward on the same config (extra keys)
-    out, lse, _, _ = fwd()
-    do = torch.randn_like(out)
-    dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    bwd = lambda: be.bwd(do, q, k, v, out, lse, dq, dk, dv, None, 0.0, scale, causal, -1, -1, 0.0, False, None, None)
-    nb = max(5, a.steps // 5)
-    for _ in range(3):
-        bwd()
-    bw = sorted(timed_windows(bwd, nb, 3, sync, world, dev))
-    ms_bwd = bw[len(bw) // 2][1]
+    out, lse = last[0][:2]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, lse)
+
+    if a.full:
+        # forward + backward on the same config (extra keys)
+        out, lse, _, _ = fwd()
+        do = torch.randn_like(out)
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        bwd = lambda: be.bwd(do, q, k, v, out, lse, dq, dk, dv, None, 0.0, scale, causal, -1, -1, 0.0, False, None, None)
+        nb = max(5, a.steps // 5)
+        for _ in range(3):
+            bwd()
+        bw = sorted(timed_windows(bwd, nb, 3, sync, world, dev))
+        ms_bwd = bw[len(bw) // 2][1]
 
     if rank == 0:
         algo_bytes = 2 * (q.numel() + k.numel() + v.numel() + out.numel()) + 4 * lse.numel()
@@ -606,19 +637,20 @@ def main(argv=None):
                          "frac": round(flops / ms / 1e9 / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": None,
                          "kernel": sched["name"], "kernel_waves_per_workgroup": sched["fwd_nw"],
                          "algorithmic_flops_per_launch": flops, "algorithmic_bytes_per_launch": algo_bytes, "kernel_ms": round(ms, 4)},
-            "fwd_bwd": {"tflops": round(3.5 * flops / (ms + ms_bwd) / 1e9, 2), "bwd_tflops": round(2.5 * flops / ms_bwd / 1e9, 2),
-                        "bwd_ms": round(ms_bwd, 4), "frac_of_peak": round(3.5 * flops / (ms + ms_bwd) / 1e9 / MFMA_BF16_PEAK_TFLOPS, 4)},
         }
+        if a.full:
+            res["fwd_bwd"] = {"tflops": round(3.5 * flops / (ms + ms_bwd) / 1e9, 2), "bwd_tflops": round(2.5 * flops / ms_bwd / 1e9, 2),
+                              "bwd_ms": round(ms_bwd, 4), "frac_of_peak": round(3.5 * flops / (ms + ms_bwd) / 1e9 / MFMA_BF16_PEAK_TFLOPS, 4)}
         # HBM traffic of the dominant kernel, measured now (two rocprofv3 --pmc passes over `bench.py --one-launch`, outside
-        # the timed region); null (with the reason) when the profiler is unavailable.
-        if world == 1 and not a.no_traffic:
+        # the timed region); null (with the reason) when the profiler is unavailable, and null without --full.
+        if a.full and world == 1 and not a.no_traffic:
             nbytes, detail = measure_traffic(sched["name"].split("::")[-1].split("<")[0])
             res["roofline"]["traffic"] = nbytes
             res["roofline"]["traffic_detail"] = detail
         # Everything beyond the contract keys goes to a side file (round 4's 13.7 KB line was cut by the driver's tail); the line keeps a compact
         # summary of it (numbers only) and the file's path.
         extras = {}
-        if world == 1 and not a.no_sweep:
+        if a.full and world == 1 and not a.no_sweep:
             extras["sweep"] = sweep(be, dev, dev_sync)
             extras["sweep_d64"] = sweep(be, dev, dev_sync, 64)
             extras["configs"] = config_rows(be, dev, dev_sync)
@@ -638,13 +670,13 @@ def main(argv=None):
             cd = extras["features"].get("causal_dropout")
             if cd:
                 res["causal_dropout"] = [cd["fwd_tflops"], cd["bwd_tflops"], cd["fwd_bwd_tflops"]]
-        if world == 1 and not a.no_parity:
+        if a.full and world == 1 and not a.no_parity:
             extras["parity"] = parity_report(be, dev, q, k, v, causal)
             t = extras["parity"].get("tensors")
             if t:
                 res["parity_max_abs_err"] = {nm: [round(t[nm][c]["max"], 6) for c in ("default", "strict", "pytorch_bf16")] for nm in t}
                 res["parity_max_abs_err"]["columns"] = "default, FA_STRICT, PyTorch bf16 -- against PyTorch fp32, all 128 units"
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             res["cpu_baseline"] = cpu_baseline(D, S, causal)
         if extras:
             res["extras_file"] = write_extras(dict(res, **extras))

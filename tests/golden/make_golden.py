@@ -139,7 +139,23 @@ def main():
     pics["cu_seqq_zero_q"] = np.array([0, 0, 256, 512], dtype=np.int32)              # test_flash_attn_ck.py:1522-1560
     pics["cu_seqq_zero_k"] = np.array([0, 503, 768, 1536], dtype=np.int32)
     np.savez_compressed(os.path.join(HERE, "known_answers.npz"), **pics)
+    concat_unpad_case()
     print("wrote fixtures to", HERE)
+
+
+def concat_unpad_case():
+    """The reference's unpad_input_for_concatenated_sequences (flash_attn/bert_padding.py) on one seeded case, inputs and outputs
+    (tests/test_bert_padding_cpu.py)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("ref_bert_padding", os.path.join(REF, "flash_attn", "bert_padding.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    torch.manual_seed(1)
+    mil = torch.tensor([[4, 1, 2, 0, 0, 0, 0, 0, 0], [9, 0, 0, 0, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 0, 0, 0, 0], [1, 1, 1, 1, 0, 0, 0, 0, 0]])
+    x = torch.randn(4, 9, 2, 8)
+    xp, idx, cu, mx = ref.unpad_input_for_concatenated_sequences(x, mil)
+    np.savez_compressed(os.path.join(HERE, "concat_unpad_ref_case.npz"), x=x.numpy(), attention_mask_in_length=mil.numpy(),
+                        hidden=xp.numpy(), indices=idx.numpy(), cu_seqlens=cu.numpy(), max_seqlen=np.array(int(mx)))
 
 
 if __name__ == "__main__":
