@@ -777,11 +777,101 @@ int do_bwd(const FaBwdParams* a, void* stream, bool varlen) {
   return FA_OK;
 }
 
+// FP8 forward (fa_fwd_fp8.hip): e4m3 q / k / v, bf16 o.  Plain attention under causal / window masks, head dims 64 / 128, fixed-length
+// and packed batches; every other feature is refused here, before any launch.
+int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool varlen) {
+  if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
+  g_err[0] = 0;
+  const char* fn = varlen ? "fa_varlen_fwd_fp8" : "fa_fwd_fp8";
+  if (a->dtype != FA_DTYPE_FP8_E4M3)
+    return fail(FA_ERR_INVALID_ARGUMENT, "%s takes FA_DTYPE_FP8_E4M3 (float8_e4m3fn) q / k / v, got dtype %d", fn, a->dtype);
+  if (a->b <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "batch size must be positive");
+  if (a->h <= 0 || a->h_k <= 0 || a->h % a->h_k != 0)
+    return fail(FA_ERR_INVALID_ARGUMENT, "Number of heads in key/value must divide number of heads in query");
+  if (a->d != 64 && a->d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
+  if (a->softcap < 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "softcap must be non-negative");
+  if (a->softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: softcap is not supported on the fp8 path", fn);
+  if (a->alibi_slopes) return fail(FA_ERR_UNSUPPORTED, "%s: ALiBi is not supported on the fp8 path", fn);
+  if (a->p_dropout != 0.f || a->rng_state) return fail(FA_ERR_UNSUPPORTED, "%s: dropout is not supported on the fp8 path", fn);
+  if (a->randval) return fail(FA_ERR_UNSUPPORTED, "%s: return_softmax is not supported on the fp8 path", fn);
+  if (a->seqused_q || a->seqused_k) return fail(FA_ERR_UNSUPPORTED, "%s: seqused_q / seqused_k are not supported on the fp8 path", fn);
+  if (a->leftpad_k) return fail(FA_ERR_UNSUPPORTED, "%s: leftpad_k is not supported on the fp8 path", fn);
+  if (a->block_table) return fail(FA_ERR_UNSUPPORTED, "%s: block_table (paged KV) is not supported on the fp8 path", fn);
+  if (a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1)
+    return fail(FA_ERR_UNSUPPORTED, "%s: the KV-cache arguments (cache_batch_idx, seqused_k_add, num_splits) have no fp8 path", fn);
+  if (!a->q || !a->k || !a->v || !a->o || !a->softmax_lse)
+    return fail(FA_ERR_INVALID_ARGUMENT, "q, k, v, o and softmax_lse must be non-NULL");
+  if (varlen != (a->cu_seqlens_q != nullptr) || varlen != (a->cu_seqlens_k != nullptr))
+    return fail(FA_ERR_INVALID_ARGUMENT, varlen ? "fa_varlen_fwd_fp8 needs cu_seqlens_q and cu_seqlens_k"
+                                                : "fa_fwd_fp8 takes fixed-length batches (cu_seqlens must be NULL)");
+  if (a->seqlen_q < 0 || a->seqlen_k < 0) return fail(FA_ERR_INVALID_ARGUMENT, "negative sequence length");
+  // 16-byte DMA pieces and stores: e4m3 rows start on 16 bytes, bf16 rows of o on 8 elements
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  if (!al16(a->q) || !al16(a->k) || !al16(a->v) || !al16(a->o)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", fn);
+  const int64_t in_strides[] = {a->q_row_stride, a->q_head_stride, a->k_row_stride, a->k_head_stride, a->v_row_stride, a->v_head_stride,
+                                varlen ? 0 : a->q_batch_stride, varlen ? 0 : a->k_batch_stride, varlen ? 0 : a->v_batch_stride};
+  for (int64_t s : in_strides)
+    if (s % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q / k / v strides must be multiples of 16 bytes", fn);
+  const int64_t o_strides[] = {a->o_row_stride, a->o_head_stride, varlen ? 0 : a->o_batch_stride};
+  for (int64_t s : o_strides)
+    if (s % 8 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: o (bf16) strides must be multiples of 8 elements", fn);
+  if (a->seqlen_q == 0 || a->total_q == 0) return FA_OK;  // nothing to write
+
+  fa::FwdK k{};
+  k.n_splits = 1;
+  k.pack_g = 1;
+  k.q = a->q; k.k = a->k; k.v = a->v; k.o = a->o; k.lse = a->softmax_lse;
+  k.q_bs = a->q_batch_stride; k.q_rs = a->q_row_stride; k.q_hs = a->q_head_stride;
+  k.k_bs = a->k_batch_stride; k.k_rs = a->k_row_stride; k.k_hs = a->k_head_stride;
+  k.v_bs = a->v_batch_stride; k.v_rs = a->v_row_stride; k.v_hs = a->v_head_stride;
+  k.o_bs = a->o_batch_stride; k.o_rs = a->o_row_stride; k.o_hs = a->o_head_stride;
+  k.cu_q = a->cu_seqlens_q; k.cu_k = a->cu_seqlens_k;
+  k.b = a->b; k.h = a->h; k.h_k = a->h_k; k.hk_ratio = a->h / a->h_k;
+  k.sq = a->seqlen_q; k.sk = a->seqlen_k; k.total_q = a->total_q;
+  int causal = a->is_causal, wl = a->window_left, wr = a->window_right;
+  normalize_window(a->seqlen_q, a->seqlen_k, false, causal, wl, wr);
+  k.wl = wl; k.wr = wr;
+  k.scale = a->softmax_scale;
+  k.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+  // P is rounded to e4m3 (largest finite value 448): the deferred rescale may let it grow to 2^thr, so thr <= 8 (P <= 256)
+  k.rescale_thr = std::min(fa::knobs().rescale_thr, 8.f);
+  constexpr int bm = 128;
+  k.nmb = (k.sq + bm - 1) / bm;
+  if (varlen) {  // uneven packed batch: enumerate the non-empty query blocks, heaviest first
+    const int64_t entries = varlen_list_entries(a, bm);
+    if (entries > 0 && a->workspace && a->workspace_bytes >= (entries + 1) * 8) {
+      fa::SchedK sk{};
+      sk.cu_a = a->cu_seqlens_q; sk.cu_o = a->cu_seqlens_k; sk.seqused_o = nullptr;
+      sk.list = (int2*)a->workspace; sk.nb = a->b; sk.blk = bm; sk.bound = (int)entries; sk.wl = wl; sk.wr = wr; sk.keys_blocked = 0;
+      sk.work_shift = fa::sched_work_shift(a->seqlen_k);
+      if (fa::launch_varlen_schedule(sk, (hipStream_t)stream) != 0)
+        return fail(FA_ERR_LAUNCH, "schedule kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+      k.work_list = (const int2*)a->workspace;
+      k.work_bound = (int)entries;
+    }
+  }
+  fa::choose_units(a->b, a->h_k, k.hk_ratio, k.nmb, k.n_units, k.unit_size, k.unit_hpx);
+  fa::Fp8K f8{};
+  if (f) {
+    f8.q_descale = f->q_descale; f8.q_bs = f->q_descale_batch_stride; f8.q_hs = f->q_descale_head_stride;
+    f8.k_descale = f->k_descale; f8.k_bs = f->k_descale_batch_stride; f8.k_hs = f->k_descale_head_stride;
+    f8.v_descale = f->v_descale; f8.v_bs = f->v_descale_batch_stride; f8.v_hs = f->v_descale_head_stride;
+  }
+  const int rc = fa::launch_fwd_fp8(k, f8, a->d, (hipStream_t)stream);
+  if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
+  if (rc == -3) return fail(FA_ERR_UNSUPPORTED, "k/v row stride too large: one 64-key tile (64 * row_stride bytes) must span less than 2 GiB");
+  if (rc != 0) return fail(FA_ERR_LAUNCH, "forward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return FA_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int fa_abi_version(void) { return FA_ABI_VERSION; }
+int fa_sizeof_fp8_params(void) { return (int)sizeof(FaFp8Params); }
+int fa_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream) { return do_fwd_fp8(params, fp8, stream, false); }
+int fa_varlen_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream) { return do_fwd_fp8(params, fp8, stream, true); }
 int fa_sizeof_fwd_params(void) { return (int)sizeof(FaFwdParams); }
 int fa_sizeof_bwd_params(void) { return (int)sizeof(FaBwdParams); }
 int fa_sizeof_kvappend_params(void) { return (int)sizeof(FaKvAppendParams); }
@@ -888,6 +978,8 @@ int fa_set_rng_state(uint64_t seed, uint64_t offset, uint64_t* rng_state, void* 
 
 int64_t fa_fwd_workspace_bytes(const FaFwdParams* params) {
   if (!params) return 0;
+  if (params->cu_seqlens_q && params->dtype == FA_DTYPE_FP8_E4M3)  // fa_varlen_fwd_fp8: 128-row blocks
+    return (varlen_list_entries(params, 128) > 0) ? (varlen_list_entries(params, 128) + 1) * 8 : 0;
   if (params->cu_seqlens_q) {  // varlen forward: the work list of an uneven packed batch
     int causal = params->is_causal, wl = params->window_left, wr = params->window_right;
     normalize_window(params->seqlen_q, params->seqlen_k, params->alibi_slopes != nullptr, causal, wl, wr);

@@ -59,6 +59,14 @@ struct FwdK {
   float rp_keep;             // 1 / (1 - p_dropout)
 };
 
+// FP8 forward (fa_fwd_fp8.hip): per-(batch, kv head) fp32 descale factors, nullptr = 1.0; element (b, hk) at ptr[b * bs + hk * hs]
+struct Fp8K {
+  const float* q_descale;
+  const float* k_descale;
+  const float* v_descale;
+  int64_t q_bs, q_hs, k_bs, k_hs, v_bs, v_hs;
+};
+
 // Fused backward (BwdK::fuse_sync, fa_bwd.hip fa_bwd_fused_kernel): int32 words of the sync area.  An error flag, 16 words reserved for the cycle statistics of
 // experiments/ablations/fa_bwd.patch, then eight control blocks -- one per XCD x, whose key-block items are those numbered x + 8k: the ready queue's tail, head and count of published
 // and unclaimed dQ items, the count of key-block items finished, the next key-block item to hand out, a 128-byte line each -- then one arrival counter per

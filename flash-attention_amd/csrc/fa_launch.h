@@ -38,7 +38,7 @@ const Knobs& knobs();
 
 // What the last fa_fwd* / fa_bwd* call of this thread launched (fa_last_schedule in the C ABI).
 struct LastSchedule {
-  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel
+  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel
   int fwd_nw;       // waves per workgroup (16 = 8-wave ping-pong)
   int fwd_feat;     // FEAT_* variant of the lock-step kernel
   int fwd_splits;   // split-KV factor
@@ -129,6 +129,9 @@ int launch_set_rng(uint64_t seed, uint64_t offset, uint64_t* dst, hipStream_t st
 int launch_fwd_il(const FwdK& p, int dtype_bf16, int d, int nw, hipStream_t stream);
 // 64-rows-per-wave forward (fa_fwd_w64.hip): 4 waves, 256 query rows per workgroup, one workgroup per CU.
 int launch_fwd_w64(const FwdK& p, int dtype_bf16, int d, hipStream_t stream);
+// FP8 (e4m3) forward (fa_fwd_fp8.hip): 4 waves, 128 query rows per workgroup, head dims 64 / 128, bf16 o.  -2 = head dim not built,
+// -3 = one 64-key tile spans >= 2 GiB.
+int launch_fwd_fp8(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
 
 // Backward: delta = rowsum(dO*O) pre-pass, dK/dV kernel (loops over query blocks),
 // dQ kernel (loops over key blocks).  Same return convention.

@@ -78,6 +78,78 @@ __global__ void cvt_probe(const float* in, unsigned short* out, int n) {
   if (t < n) { __bf16 x = (__bf16)in[t]; out[t] = *(unsigned short*)&x; }
 }
 
+// ---- FP8 (OCP e4m3) forms the fp8 forward (fa_fwd_fp8.hip) relies on
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(2))) int i32x2;
+// v_mfma_scale_f32_32x32x64_f8f6f4, e4m3 A and B, unit scales.  A 32x64, B 64x32 row-major bytes; ASSUMED maps:
+//   A: byte j of lane l = A[l&31][32*(l>>5) + j];  B: byte j of lane l = B[32*(l>>5) + j][l&31];  D as the bf16 form.
+__global__ void mfma_scale_e4m3(const unsigned char* A, const unsigned char* B, float* D) {
+  int l = threadIdx.x, hi = l >> 5, c = l & 31;
+  i32x8 a, b;
+  for (int w = 0; w < 8; ++w) {
+    unsigned ua = 0, ub = 0;
+    for (int t = 0; t < 4; ++t) { int j = 4 * w + t; ua |= (unsigned)A[c * 64 + 32 * hi + j] << (8 * t); ub |= (unsigned)B[(32 * hi + j) * 32 + c] << (8 * t); }
+    a[w] = (int)ua; b[w] = (int)ub;
+  }
+  f32x16 acc = {};
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 0, 0, 0, 127, 0, 127);
+  for (int r = 0; r < 16; ++r) D[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + c] = acc[r];
+}
+// The fp8 forward's P.V step: the accumulator tiles of P^T (lane = query q, register r of tile s = key 32 s + (r&3) + 8 (r>>2) + 4 (l>>5))
+// packed with v_cvt_pk_fp8_f32 into the B operand, V^T as the A operand with byte j of lane (d, h) = V[32 (j>>4) + 8 ((j>>2)&3) + 4 h + (j&3)][d].
+// P (32 queries x 64 keys) and V (64 keys x 32 columns) row-major floats, exactly representable in e4m3; O^T[d][q] out.
+__global__ void pv_e4m3(const float* P, const unsigned char* V, float* OT) {
+  int l = threadIdx.x, h = l >> 5, c = l & 31;
+  i32x8 pf, vt;
+  for (int s = 0; s < 2; ++s)
+    for (int g = 0; g < 4; ++g) {
+      float x[4];
+      for (int t = 0; t < 4; ++t) { int r = 4 * g + t; x[t] = P[c * 64 + 32 * s + (r & 3) + 8 * (r >> 2) + 4 * h]; }
+      int w = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
+      pf[4 * s + g] = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], w, true);
+    }
+  for (int w = 0; w < 8; ++w) {
+    unsigned u = 0;
+    for (int t = 0; t < 4; ++t) { int j = 4 * w + t; u |= (unsigned)V[(32 * (j >> 4) + 8 * ((j >> 2) & 3) + 4 * h + (j & 3)) * 32 + c] << (8 * t); }
+    vt[w] = (int)u;
+  }
+  f32x16 acc = {};
+  acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(vt, pf, acc, 0, 0, 0, 127, 0, 127);
+  for (int r = 0; r < 16; ++r) OT[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + c] = acc[r];
+}
+// v_cvt_pk_fp8_f32: word_sel 0 writes bytes 0 (src0) and 1 (src1) and keeps bytes 2-3; word_sel 1 writes bytes 2 and 3 and keeps 0-1
+__global__ void cvt_fp8_probe(const float* in, unsigned* out) {
+  int t = threadIdx.x;
+  if (t < 8) {
+    out[2 * t] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(in[2 * t], in[2 * t + 1], (int)0xAABBCCDDu, false);
+    out[2 * t + 1] = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(in[2 * t], in[2 * t + 1], (int)0xAABBCCDDu, true);
+  }
+}
+// ds_read_b64_tr_b8: ASSUMED, by analogy with the 16-bit form: inside each 16-lane group, lane i supplies the address of row i>>1,
+// bytes 8*(i&1)..+7 of an 8 x 16 block of bytes, and receives column i (byte j = row j).
+__global__ void tr8_probe(unsigned char* out) {
+  __shared__ __attribute__((aligned(16))) unsigned char lds[4 * 128];
+  int l = threadIdx.x;
+  for (int i = l; i < 4 * 128; i += 64) lds[i] = (unsigned char)(i & 127);   // one 8 x 16 block per lane group, byte (r, c) = 16 r + c
+  __syncthreads();
+  int g = l >> 4, i = l & 15;
+  i32x2 v = __builtin_amdgcn_ds_read_tr8_b64_v2i32((__attribute__((address_space(3))) i32x2*)(lds + 128 * g + 8 * i));
+  for (int j = 0; j < 8; ++j) out[l * 8 + j] = (unsigned char)(((unsigned)v[j >> 2] >> (8 * (j & 3))) & 0xFF);
+}
+// OCP e4m3 (bias 7, no infinities, 448 = largest finite), round to nearest even; |f| <= 448
+static unsigned char f2e4m3(float f) {
+  unsigned char s = f < 0 ? 0x80 : 0;
+  float a = fabsf(f);
+  if (a == 0.f) return s;
+  int e;
+  frexpf(a, &e);       // a = m 2^e, m in [0.5, 1)
+  int E = e - 1 + 7;   // biased exponent of the 1.xxx form
+  if (E < 1) return s | (unsigned char)rintf(a * 512.f);   // subnormal: k 2^-9 (k = 8 is the smallest normal, 0x08)
+  float r = rintf((a / ldexpf(1.f, e - 1) - 1.f) * 8.f);
+  if (r == 8.f) { r = 0.f; E += 1; }
+  return s | (unsigned char)(E << 3) | (unsigned char)r;
+}
+
 static float bf2f(unsigned short b) { unsigned u = (unsigned)b << 16; float f; memcpy(&f, &u, 4); return f; }
 static unsigned short f2bf(float f) { unsigned u; memcpy(&u, &f, 4); u += 0x7FFF + ((u >> 16) & 1); return (unsigned short)(u >> 16); }
 static unsigned short f2h(float f) { _Float16 h = (_Float16)f; unsigned short s; memcpy(&s, &h, 2); return s; }
@@ -158,6 +230,54 @@ int main() {
     unsigned short o[n]; CK(hipMemcpy(o, dout, n * 2, hipMemcpyDeviceToHost));
     int bad = 0; for (int i = 0; i < n; ++i) bad += (o[i] != f2bf(in[i]));
     printf("[float->bf16 is RNE] %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+  }
+  {  // scaled fp8 MFMA: A / B / D maps on exact integer data, asymmetric B
+    std::vector<float> A(32 * 64), B(64 * 32), Dref(32 * 32, 0.f);
+    for (auto& x : A) x = (float)(rand() % 17 - 8);
+    for (int kk = 0; kk < 64; ++kk) for (int n = 0; n < 32; ++n) B[kk * 32 + n] = (float)((kk * 7 + n * 3) % 13 - 6) + (n > kk % 32 ? 0.5f : 0.f);
+    for (int m = 0; m < 32; ++m) for (int n = 0; n < 32; ++n) { float s = 0; for (int kk = 0; kk < 64; ++kk) s += A[m * 64 + kk] * B[kk * 32 + n]; Dref[m * 32 + n] = s; }
+    std::vector<unsigned char> A8(2048), B8(2048);
+    for (int i = 0; i < 2048; ++i) { A8[i] = f2e4m3(A[i]); B8[i] = f2e4m3(B[i]); }
+    unsigned char *dA, *dB; float* dD; CK(hipMalloc(&dA, 2048)); CK(hipMalloc(&dB, 2048)); CK(hipMalloc(&dD, 4096));
+    CK(hipMemcpy(dA, A8.data(), 2048, hipMemcpyHostToDevice)); CK(hipMemcpy(dB, B8.data(), 2048, hipMemcpyHostToDevice));
+    mfma_scale_e4m3<<<1, 64>>>(dA, dB, dD); CK(hipDeviceSynchronize());
+    std::vector<float> D(1024); CK(hipMemcpy(D.data(), dD, 4096, hipMemcpyDeviceToHost));
+    int bad = 0; for (int i = 0; i < 1024; ++i) bad += (D[i] != Dref[i]);
+    printf("[mfma_scale_f32_32x32x64_f8f6f4 e4m3 A/B/D maps] %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+    // the P.V step of the fp8 forward: accumulator-layout P^T packed by v_cvt_pk_fp8_f32, V^T in the permuted key order
+    std::vector<float> P(32 * 64), V(64 * 32), OT(32 * 32, 0.f);
+    const float pv[8] = {0.f, 1.f, 0.5f, 2.f, 0.25f, 3.f, 1.5f, 0.125f};
+    for (int i = 0; i < 2048; ++i) { P[i] = pv[rand() % 8]; V[i] = (float)(rand() % 15 - 7); }
+    for (int d = 0; d < 32; ++d) for (int q = 0; q < 32; ++q) { float s = 0; for (int kk = 0; kk < 64; ++kk) s += V[kk * 32 + d] * P[q * 64 + kk]; OT[d * 32 + q] = s; }
+    std::vector<unsigned char> V8(2048);
+    for (int i = 0; i < 2048; ++i) V8[i] = f2e4m3(V[i]);
+    float* dP; CK(hipMalloc(&dP, 8192));
+    CK(hipMemcpy(dP, P.data(), 8192, hipMemcpyHostToDevice)); CK(hipMemcpy(dA, V8.data(), 2048, hipMemcpyHostToDevice));
+    pv_e4m3<<<1, 64>>>(dP, dA, dD); CK(hipDeviceSynchronize());
+    CK(hipMemcpy(D.data(), dD, 4096, hipMemcpyDeviceToHost));
+    bad = 0; for (int i = 0; i < 1024; ++i) bad += (D[i] != OT[i]);
+    printf("[fp8 forward P.V step: cvt_pk_fp8 P^T as B, permuted V^T as A] %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+  }
+  {  // v_cvt_pk_fp8_f32 byte placement and rounding (OCP e4m3, RNE)
+    const float in[16] = {1.f, 2.f, -1.f, 448.f, 0.5f, 3.f, 1.0625f, 1.1875f, 0.001953125f, -0.0009765625f, 240.f, 1e-12f, 13.f, -0.3f, 100.f, 0.0178f};
+    float* di; unsigned* dout; CK(hipMalloc(&di, 64)); CK(hipMalloc(&dout, 64));
+    CK(hipMemcpy(di, in, 64, hipMemcpyHostToDevice)); cvt_fp8_probe<<<1, 64>>>(di, dout); CK(hipDeviceSynchronize());
+    unsigned o[16]; CK(hipMemcpy(o, dout, 64, hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int t = 0; t < 8; ++t) {
+      const unsigned lo = f2e4m3(in[2 * t]) | ((unsigned)f2e4m3(in[2 * t + 1]) << 8);
+      bad += (o[2 * t] != (0xAABB0000u | lo)) + (o[2 * t + 1] != ((lo << 16) | 0xCCDDu));
+    }
+    printf("[v_cvt_pk_fp8_f32 byte placement / e4m3 RNE] %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+    if (bad) for (int t = 0; t < 8; ++t) printf("  (%g, %g): word_sel 0 -> %08x, 1 -> %08x\n", in[2 * t], in[2 * t + 1], o[2 * t], o[2 * t + 1]);
+  }
+  {  // ds_read_b64_tr_b8
+    unsigned char* d; CK(hipMalloc(&d, 512)); tr8_probe<<<1, 64>>>(d); CK(hipDeviceSynchronize());
+    unsigned char R[512]; CK(hipMemcpy(R, d, 512, hipMemcpyDeviceToHost));
+    int bad = 0;
+    for (int l = 0; l < 64; ++l) for (int j = 0; j < 8; ++j) bad += (R[l * 8 + j] != (unsigned char)(16 * j + (l & 15)));
+    printf("[ds_read_b64_tr_b8 lane map] %s (%d mismatches)\n", bad ? "FAIL" : "PASS", bad); fails += bad != 0;
+    if (bad) for (int l = 0; l < 16; ++l) printf("  %2d: %3d %3d %3d %3d %3d %3d %3d %3d\n", l, R[l * 8], R[l * 8 + 1], R[l * 8 + 2], R[l * 8 + 3], R[l * 8 + 4], R[l * 8 + 5], R[l * 8 + 6], R[l * 8 + 7]);
   }
   printf("PROBE %s\n", fails ? "FAILED" : "ALL PASS");
   return fails ? 1 : 0;

@@ -607,6 +607,114 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
   return {out, lse};
 }
 
+// ---- FP8 forward (FA3's fp8 contract, hopper/flash_api.cpp:694-696 and :859-863): float8_e4m3fn q / k / v, optional fp32 (B, Hk) descales with any
+// strides, bf16 out.  Two names beyond the reference's five (fwd_fp8 / varlen_fwd_fp8), so that its positional orders stay untouched.
+void fp8_checks(const Tensor& q, const Tensor& k, const Tensor& v) {
+  CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
+  TORCH_CHECK(q.dtype() == at::kFloat8_e4m3fn && k.dtype() == at::kFloat8_e4m3fn && v.dtype() == at::kFloat8_e4m3fn,
+              "fwd_fp8: q, k and v must have dtype torch.float8_e4m3fn");
+  TORCH_CHECK(q.stride(-1) == 1 && k.stride(-1) == 1 && v.stride(-1) == 1, "Input tensor must have contiguous last dimension");
+}
+void fp8_descale(FaFp8Params& f, int which, const OptTensor& t, int64_t B, int64_t Hk) {
+  if (!t.has_value()) return;
+  static const char* names[3] = {"q_descale", "k_descale", "v_descale"};
+  TORCH_CHECK(t->dtype() == at::kFloat, names[which], " must have dtype float32");
+  CHECK_DEVICE(*t);
+  TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == Hk, names[which], " must have shape (batch_size, num_heads_k)");
+  const float* p = t->data_ptr<float>();
+  if (which == 0) { f.q_descale = p; f.q_descale_batch_stride = t->stride(0); f.q_descale_head_stride = t->stride(1); }
+  if (which == 1) { f.k_descale = p; f.k_descale_batch_stride = t->stride(0); f.k_descale_head_stride = t->stride(1); }
+  if (which == 2) { f.v_descale = p; f.v_descale_batch_stride = t->stride(0); f.v_descale_head_stride = t->stride(1); }
+}
+Tensor fp8_out(const OptTensor& out_, const Tensor& q, at::IntArrayRef shape) {
+  if (!out_.has_value()) return at::empty(shape, q.options().dtype(at::kBFloat16));
+  TORCH_CHECK(out_->dtype() == at::kBFloat16, "For FP8 input, output must have dtype BF16");
+  CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_);
+  TORCH_CHECK(out_->sizes() == shape, "out_ must have the shape of q");
+  return *out_;
+}
+
+std::vector<Tensor> mha_fwd_fp8(const Tensor& q, const Tensor& k, const Tensor& v, OptTensor& out_, const OptTensor& q_descale,
+                                const OptTensor& k_descale, const OptTensor& v_descale, const double softmax_scale, bool is_causal,
+                                int64_t window_size_left, int64_t window_size_right) {
+  fp8_checks(q, k, v);
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "q, k, v must be 4-D (batch, seqlen, nheads, headdim)");
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1), Hk = k.size(2);
+  TORCH_CHECK(B > 0, "batch size must be positive");
+  TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  CHECK_SHAPE(k, B, Sk, Hk, D);
+  CHECK_SHAPE(v, B, Sk, Hk, D);
+  c10::DeviceGuard guard(q.device());
+  FaFp8Params f{};
+  fp8_descale(f, 0, q_descale, B, Hk); fp8_descale(f, 1, k_descale, B, Hk); fp8_descale(f, 2, v_descale, B, Hk);
+  Tensor out = fp8_out(out_, q, {B, Sq, H, D});
+  Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (Sk == 0) {
+    out.zero_();
+    lse.fill_(std::numeric_limits<float>::infinity());
+  } else if (Sq > 0) {
+    FaFwdParams a{};
+    a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr(); a.o = out.data_ptr(); a.softmax_lse = lse.data_ptr<float>();
+    a.q_batch_stride = q.stride(0); a.q_row_stride = q.stride(1); a.q_head_stride = q.stride(2);
+    a.k_batch_stride = k.stride(0); a.k_row_stride = k.stride(1); a.k_head_stride = k.stride(2);
+    a.v_batch_stride = v.stride(0); a.v_row_stride = v.stride(1); a.v_head_stride = v.stride(2);
+    a.o_batch_stride = out.stride(0); a.o_row_stride = out.stride(1); a.o_head_stride = out.stride(2);
+    a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = Sq; a.seqlen_k = Sk; a.total_q = B * Sq;
+    a.dtype = FA_DTYPE_FP8_E4M3;
+    a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
+    a.softmax_scale = (float)softmax_scale;
+    fa_check(fa_fwd_fp8(&a, &f, cur_stream(q)));
+  }
+  return {out, lse};
+}
+
+std::vector<Tensor> mha_varlen_fwd_fp8(const Tensor& q, const Tensor& k, const Tensor& v, OptTensor& out_, const Tensor& cu_seqlens_q,
+                                       const Tensor& cu_seqlens_k, int64_t max_seqlen_q, int64_t max_seqlen_k, const OptTensor& q_descale,
+                                       const OptTensor& k_descale, const OptTensor& v_descale, const double softmax_scale, bool is_causal,
+                                       int64_t window_size_left, int64_t window_size_right) {
+  fp8_checks(q, k, v);
+  TORCH_CHECK(cu_seqlens_q.dtype() == at::kInt && cu_seqlens_k.dtype() == at::kInt, "cu_seqlens_q/k must have dtype int32");
+  CHECK_DEVICE(cu_seqlens_q); CHECK_DEVICE(cu_seqlens_k);
+  TORCH_CHECK(cu_seqlens_q.is_contiguous() && cu_seqlens_k.is_contiguous(), "cu_seqlens_q/k must be contiguous");
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "q, k, v must be 3-D (total, nheads, headdim)");
+  const int64_t total_q = q.size(0), H = q.size(1), D = q.size(2), total_k = k.size(0), Hk = k.size(1);
+  const int64_t B = cu_seqlens_q.numel() - 1;
+  TORCH_CHECK(B > 0, "batch size must be positive");
+  CHECK_SHAPE(cu_seqlens_k, B + 1);
+  TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  CHECK_SHAPE(k, total_k, Hk, D);
+  CHECK_SHAPE(v, total_k, Hk, D);
+  c10::DeviceGuard guard(q.device());
+  FaFp8Params f{};
+  fp8_descale(f, 0, q_descale, B, Hk); fp8_descale(f, 1, k_descale, B, Hk); fp8_descale(f, 2, v_descale, B, Hk);
+  Tensor out = fp8_out(out_, q, {total_q, H, D});
+  Tensor lse = at::empty({H, total_q}, q.options().dtype(at::kFloat));
+  if (max_seqlen_k == 0 || total_k == 0) {
+    out.zero_();
+    lse.fill_(std::numeric_limits<float>::infinity());
+  } else if (total_q > 0 && max_seqlen_q > 0) {
+    FaFwdParams a{};
+    a.q = q.data_ptr(); a.k = k.data_ptr(); a.v = v.data_ptr(); a.o = out.data_ptr(); a.softmax_lse = lse.data_ptr<float>();
+    a.q_row_stride = q.stride(0); a.q_head_stride = q.stride(1);
+    a.k_row_stride = k.stride(0); a.k_head_stride = k.stride(1);
+    a.v_row_stride = v.stride(0); a.v_head_stride = v.stride(1);
+    a.o_row_stride = out.stride(0); a.o_head_stride = out.stride(1);
+    a.cu_seqlens_q = cu_seqlens_q.data_ptr<int>(); a.cu_seqlens_k = cu_seqlens_k.data_ptr<int>();
+    a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = (int)max_seqlen_q; a.seqlen_k = (int)max_seqlen_k; a.total_q = total_q;
+    a.dtype = FA_DTYPE_FP8_E4M3;
+    a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
+    a.softmax_scale = (float)softmax_scale;
+    Tensor ws;  // work list of an uneven packed batch (0 bytes = dense grid)
+    const int64_t ws_bytes = fa_fwd_workspace_bytes(&a);
+    if (ws_bytes > 0) {
+      ws = at::empty({ws_bytes}, q.options().dtype(at::kByte));
+      a.workspace = ws.data_ptr(); a.workspace_bytes = ws_bytes;
+    }
+    fa_check(fa_varlen_fwd_fp8(&a, &f, cur_stream(q)));
+  }
+  return {out, lse};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -621,4 +729,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bwd", &mha_bwd, "Backward pass");
   m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
   m.def("fwd_kvcache", &mha_fwd_kvcache, "Forward pass, with KV-cache");
+  m.def("fwd_fp8", &mha_fwd_fp8, "Forward pass, FP8 (e4m3) inputs with per-(batch, kv head) descales, bf16 output");
+  m.def("varlen_fwd_fp8", &mha_varlen_fwd_fp8, "Forward pass (variable length), FP8 (e4m3) inputs with per-(batch, kv head) descales, bf16 output");
 }

@@ -11,7 +11,7 @@ import ctypes as C
 import os
 
 FA_ABI_VERSION = 6
-FA_DTYPE_FP16, FA_DTYPE_BF16 = 0, 1
+FA_DTYPE_FP16, FA_DTYPE_BF16, FA_DTYPE_FP8_E4M3 = 0, 1, 2
 FA_OK, FA_ERR_INVALID_ARGUMENT, FA_ERR_UNSUPPORTED, FA_ERR_LAUNCH, FA_ERR_WORKSPACE = 0, -1, -2, -3, -4
 
 _i64, _i32, _f32, _vp = C.c_int64, C.c_int32, C.c_float, C.c_void_p
@@ -35,6 +35,15 @@ class FaFwdParams(C.Structure):
         ("rng_state", _vp), ("randval", _vp),
         ("randval_batch_stride", _i64), ("randval_head_stride", _i64), ("randval_row_stride", _i64),
         ("workspace", _vp), ("workspace_bytes", _i64), ("leftpad_k", _vp), ("seqused_q", _vp),
+    ]
+
+
+class FaFp8Params(C.Structure):
+    _fields_ = [
+        ("q_descale", _vp), ("k_descale", _vp), ("v_descale", _vp),
+        ("q_descale_batch_stride", _i64), ("q_descale_head_stride", _i64),
+        ("k_descale_batch_stride", _i64), ("k_descale_head_stride", _i64),
+        ("v_descale_batch_stride", _i64), ("v_descale_head_stride", _i64),
     ]
 
 
@@ -89,6 +98,7 @@ EXPORTS = (
     "fa_last_error", "fa_rotary", "fa_knobs_reload", "fa_last_schedule", "fa_last_kernel_name", "fa_fwd_schedule_query", "fa_bwd_dq_schedule_query", "fa_bwd_plan_query",
     "fa_fwd", "fa_varlen_fwd", "fa_fwd_kvcache", "fa_kvcache_append", "fa_set_rng_state", "fa_fwd_workspace_bytes",
     "fa_bwd_workspace_bytes", "fa_bwd", "fa_varlen_bwd", "fa_bwd_fused_status",
+    "fa_sizeof_fp8_params", "fa_fwd_fp8", "fa_varlen_fwd_fp8",
 )
 
 _LIB = None
@@ -129,6 +139,10 @@ def load():
         fn.argtypes = [C.POINTER(FaBwdParams), C.c_void_p]
         fn.restype = C.c_int
     lib.fa_sizeof_rotary_params.restype = C.c_int
+    lib.fa_sizeof_fp8_params.restype = C.c_int
+    for fn in (lib.fa_fwd_fp8, lib.fa_varlen_fwd_fp8):
+        fn.argtypes = [C.POINTER(FaFwdParams), C.POINTER(FaFp8Params), C.c_void_p]
+        fn.restype = C.c_int
     lib.fa_knobs_reload.argtypes = []
     lib.fa_knobs_reload.restype = None
     lib.fa_last_schedule.argtypes = [C.POINTER(C.c_int32), C.c_int]
@@ -154,7 +168,8 @@ def load():
         raise ImportError(f"{path}: ABI version {lib.fa_abi_version()} != binder {FA_ABI_VERSION}")
     if (lib.fa_sizeof_fwd_params() != C.sizeof(FaFwdParams) or lib.fa_sizeof_bwd_params() != C.sizeof(FaBwdParams)
             or lib.fa_sizeof_kvappend_params() != C.sizeof(FaKvAppendParams)
-            or lib.fa_sizeof_rotary_params() != C.sizeof(FaRotaryParams)):
+            or lib.fa_sizeof_rotary_params() != C.sizeof(FaRotaryParams)
+            or lib.fa_sizeof_fp8_params() != C.sizeof(FaFp8Params)):
         raise ImportError(f"{path}: parameter-block size mismatch with the ctypes mirror")
     _LIB = lib
     return lib

@@ -26,7 +26,7 @@ def reload_knobs() -> None:
 
 
 _SCHED_FIELDS = ("fwd_kernel", "fwd_nw", "fwd_feat", "fwd_splits", "fwd_list", "d", "bf16", "bwd_dq_nw", "bwd_list", "bwd_spill", "fwd_pack", "bwd_dkdv_nw")
-FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel"}
+FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel"}
 
 
 def last_schedule() -> dict:
@@ -289,6 +289,107 @@ def varlen_fwd(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, leftpad_k_,
                 a.workspace, a.workspace_bytes = _ptr(ws), ws_bytes
             _cabi.check(lib.fa_varlen_fwd(C.byref(a), C.c_void_p(_stream_ptr(q.device))))
     return [out, lse, p_out, rng_state]
+
+
+def _fp8_args(q, k, v, out_, descales, batch, nheads_k, out_shape):
+    """Checks shared by fwd_fp8 / varlen_fwd_fp8 (FA3's fp8 contract, hopper/flash_api.cpp:694-696, :859-863) -> (out, FaFp8Params)."""
+    _check_dev(q, k, v)
+    if not (q.dtype == k.dtype == v.dtype == torch.float8_e4m3fn):
+        raise RuntimeError("fwd_fp8: q, k and v must have dtype torch.float8_e4m3fn")
+    for t in (q, k, v):
+        if t.stride(-1) != 1:
+            raise RuntimeError("Input tensor must have contiguous last dimension")
+    f = _cabi.FaFp8Params()
+    for name, t in zip(("q_descale", "k_descale", "v_descale"), descales):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or tuple(t.shape) != (batch, nheads_k):
+            raise RuntimeError(f"{name} must be a float32 tensor of shape (batch_size, num_heads_k) = ({batch}, {nheads_k})")
+        _check_dev(t)
+        setattr(f, name, _ptr(t))
+        setattr(f, name + "_batch_stride", t.stride(0))
+        setattr(f, name + "_head_stride", t.stride(1))
+    if out_ is not None:
+        if out_.dtype != torch.bfloat16 or tuple(out_.shape) != out_shape or out_.stride(-1) != 1:
+            raise RuntimeError("out_ of the fp8 forward must be bf16, shaped like q, with a contiguous last dimension")
+        _check_dev(out_)
+    out = out_ if out_ is not None else torch.empty(out_shape, dtype=torch.bfloat16, device=q.device)
+    return out, f
+
+
+def fwd_fp8(q, k, v, out_, q_descale, k_descale, v_descale, softmax_scale, is_causal, window_size_left,
+            window_size_right) -> List[torch.Tensor]:
+    """FP8 forward (C ABI fa_fwd_fp8): q (B,Sq,H,D), k/v (B,Sk,Hk,D) float8_e4m3fn, optional fp32 (B,Hk) descales -> [out bf16, softmax_lse]."""
+    B, Sq, H, D = q.shape
+    Sk, Hk = k.shape[1], k.shape[2]
+    if tuple(k.shape) != (B, Sk, Hk, D) or tuple(v.shape) != (B, Sk, Hk, D):
+        raise RuntimeError("key/value shape mismatch")
+    if H % Hk != 0:
+        raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    out, f = _fp8_args(q, k, v, out_, (q_descale, k_descale, v_descale), B, Hk, (B, Sq, H, D))
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    if Sk == 0:
+        out.zero_()
+        lse.fill_(float("inf"))
+    elif Sq > 0:
+        a = _cabi.FaFwdParams()
+        a.q, a.k, a.v, a.o, a.softmax_lse = _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse)
+        a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+        a.k_batch_stride, a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1), k.stride(2)
+        a.v_batch_stride, a.v_row_stride, a.v_head_stride = v.stride(0), v.stride(1), v.stride(2)
+        a.o_batch_stride, a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
+        a.b, a.h, a.h_k, a.d = B, H, Hk, D
+        a.seqlen_q, a.seqlen_k, a.total_q = Sq, Sk, B * Sq
+        a.dtype = _cabi.FA_DTYPE_FP8_E4M3
+        a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)
+        a.softmax_scale = float(softmax_scale)
+        with torch.cuda.device(q.device):
+            _cabi.check(_cabi.load().fa_fwd_fp8(C.byref(a), C.byref(f), C.c_void_p(_stream_ptr(q.device))))
+    return [out, lse]
+
+
+def varlen_fwd_fp8(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale, v_descale,
+                   softmax_scale, is_causal, window_size_left, window_size_right) -> List[torch.Tensor]:
+    """FP8 forward of a packed batch (C ABI fa_varlen_fwd_fp8): q (total_q,H,D), k/v (total_k,Hk,D) float8_e4m3fn -> [out bf16, softmax_lse (H,total_q)]."""
+    for cu in (cu_seqlens_q, cu_seqlens_k):
+        if cu.dtype != torch.int32 or not cu.is_contiguous():
+            raise RuntimeError("cu_seqlens_q/k must be contiguous int32 tensors")
+    _check_dev(cu_seqlens_q, cu_seqlens_k)
+    total_q, H, D = q.shape
+    total_k, Hk = k.shape[0], k.shape[1]
+    B = cu_seqlens_q.numel() - 1
+    if B <= 0 or cu_seqlens_k.numel() != B + 1:
+        raise RuntimeError("cu_seqlens_q/k must have shape (batch_size + 1) with batch_size > 0")
+    if tuple(k.shape) != (total_k, Hk, D) or tuple(v.shape) != (total_k, Hk, D):
+        raise RuntimeError("key/value shape mismatch")
+    if H % Hk != 0:
+        raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    out, f = _fp8_args(q, k, v, out_, (q_descale, k_descale, v_descale), B, Hk, (total_q, H, D))
+    lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
+    if max_seqlen_k == 0 or total_k == 0:
+        out.zero_()
+        lse.fill_(float("inf"))
+    elif total_q > 0 and max_seqlen_q > 0:
+        a = _cabi.FaFwdParams()
+        a.q, a.k, a.v, a.o, a.softmax_lse = _ptr(q), _ptr(k), _ptr(v), _ptr(out), _ptr(lse)
+        a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1)
+        a.k_row_stride, a.k_head_stride = k.stride(0), k.stride(1)
+        a.v_row_stride, a.v_head_stride = v.stride(0), v.stride(1)
+        a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1)
+        a.cu_seqlens_q, a.cu_seqlens_k = _ptr(cu_seqlens_q), _ptr(cu_seqlens_k)
+        a.b, a.h, a.h_k, a.d = B, H, Hk, D
+        a.seqlen_q, a.seqlen_k, a.total_q = int(max_seqlen_q), int(max_seqlen_k), total_q
+        a.dtype = _cabi.FA_DTYPE_FP8_E4M3
+        a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)
+        a.softmax_scale = float(softmax_scale)
+        with torch.cuda.device(q.device):
+            lib = _cabi.load()
+            ws_bytes = lib.fa_fwd_workspace_bytes(C.byref(a))  # work list of an uneven packed batch (0 = dense grid)
+            if ws_bytes > 0:
+                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
+                a.workspace, a.workspace_bytes = _ptr(ws), ws_bytes
+            _cabi.check(lib.fa_varlen_fwd_fp8(C.byref(a), C.byref(f), C.c_void_p(_stream_ptr(q.device))))
+    return [out, lse]
 
 
 def _bwd_out(buf, like, name):

@@ -171,6 +171,36 @@ def _padded_bwd_fake(dout, q, k, v, out, softmax_lse, dq, dk, dv, cu_seqlens_q, 
     return torch.empty((H, total_q), dtype=torch.float32, device=q.device)
 
 
+def _fwd_fp8_impl(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_descale: Optional[torch.Tensor], k_descale: Optional[torch.Tensor],
+                  v_descale: Optional[torch.Tensor], softmax_scale: float, causal: bool, window_size_left: int,
+                  window_size_right: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    out, lse = flash_attn_gpu.fwd_fp8(q, k, v, None, q_descale, k_descale, v_descale, softmax_scale, causal, window_size_left,
+                                      window_size_right)
+    return out, lse
+
+
+def _fwd_fp8_fake(q, k, v, q_descale, k_descale, v_descale, softmax_scale, causal, window_size_left, window_size_right):
+    B, Sq, H, D = q.shape
+    return (torch.empty((B, Sq, H, D), dtype=torch.bfloat16, device=q.device),
+            torch.empty((B, H, Sq), dtype=torch.float32, device=q.device))
+
+
+def _varlen_fwd_fp8_impl(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqlens_q: torch.Tensor, cu_seqlens_k: torch.Tensor,
+                         max_seqlen_q: int, max_seqlen_k: int, q_descale: Optional[torch.Tensor], k_descale: Optional[torch.Tensor],
+                         v_descale: Optional[torch.Tensor], softmax_scale: float, causal: bool, window_size_left: int,
+                         window_size_right: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    out, lse = flash_attn_gpu.varlen_fwd_fp8(q, k, v, None, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale,
+                                             v_descale, softmax_scale, causal, window_size_left, window_size_right)
+    return out, lse
+
+
+def _varlen_fwd_fp8_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale, v_descale, softmax_scale,
+                         causal, window_size_left, window_size_right):
+    total_q, H, D = q.shape
+    return (torch.empty((total_q, H, D), dtype=torch.bfloat16, device=q.device),
+            torch.empty((H, total_q), dtype=torch.float32, device=q.device))
+
+
 def _register(name, impl, fake, mutates=()):
     op = torch.library.custom_op(f"flash_attn_amd::{name}", impl, mutates_args=mutates, device_types="cuda")
     op.register_fake(fake)
@@ -183,6 +213,27 @@ _flash_attn_backward = _register("_flash_attn_backward", _bwd_impl, _bwd_fake, (
 _flash_attn_padded_forward = _register("_flash_attn_padded_forward", _padded_fwd_impl, _padded_fwd_fake)
 _flash_attn_padded_backward = _register("_flash_attn_padded_backward", _padded_bwd_impl, _padded_bwd_fake, ("dq", "dk", "dv"))
 _flash_attn_varlen_backward = _register("_flash_attn_varlen_backward", _varlen_bwd_impl, _varlen_bwd_fake, ("dq", "dk", "dv"))
+_flash_attn_fp8_forward = _register("_flash_attn_fp8_forward", _fwd_fp8_impl, _fwd_fp8_fake)
+_flash_attn_varlen_fp8_forward = _register("_flash_attn_varlen_fp8_forward", _varlen_fwd_fp8_impl, _varlen_fwd_fp8_fake)
+
+
+def _fp8_route(q, k, v, batch, dropout_p, softmax_scale, softcap, alibi_slopes, descales):
+    """FP8 inputs (FA3's contract): q / k / v float8_e4m3fn, descales fp32 (B, Hk) or None, forward only.  The checks read shapes and flags
+    only, so they run under fake tensors (torch.compile / export) as well.  Returns the softmax scale."""
+    fp8 = torch.float8_e4m3fn
+    if q.dtype != fp8:
+        raise RuntimeError("q_descale / k_descale / v_descale apply to float8_e4m3fn inputs only")
+    if k.dtype != fp8 or v.dtype != fp8:
+        raise RuntimeError("query, key and value must have the same dtype")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise RuntimeError("the fp8 forward has no backward: call it under torch.no_grad() or on tensors that do not require grad")
+    if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None:
+        raise RuntimeError("the fp8 forward supports neither dropout, softcap nor ALiBi")
+    hk = k.shape[-2]
+    for name, t in zip(("q_descale", "k_descale", "v_descale"), descales):
+        if t is not None and tuple(t.shape) != (batch, hk):
+            raise RuntimeError(f"{name} must have shape (batch_size, num_heads_k) = ({batch}, {hk}), got {tuple(t.shape)}")
+    return q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale
 
 
 # An exported program (torch.export) holds the raw ops, not the autograd.Function wrappers below; with an autograd formula on
@@ -368,10 +419,16 @@ def flash_attn_padded_func(q, k, v, seqlens_q, seqlens_k=None, starts_q=None, st
 
 
 def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0,
-                    alibi_slopes=None, deterministic=False, return_attn_probs=False):
+                    alibi_slopes=None, deterministic=False, return_attn_probs=False, *, q_descale=None, k_descale=None, v_descale=None):
     """q (B,Sq,H,D); k, v (B,Sk,Hk,D) with H % Hk == 0 (MQA/GQA).  Causal / window masks are aligned to the
     bottom-right corner; ``window_size=(l, r)`` lets query i see keys [i+Sk-Sq-l, i+Sk-Sq+r].
-    Returns out (B,Sq,H,D) (and softmax_lse (B,H,Sq), S_dmask when ``return_attn_probs``)."""
+    Returns out (B,Sq,H,D) (and softmax_lse (B,H,Sq), S_dmask when ``return_attn_probs``).
+    float8_e4m3fn q / k / v (FA3's fp8 forward): optional fp32 (B, Hk) ``q_descale`` / ``k_descale`` / ``v_descale``, bf16 out, forward only
+    (head dims 64 / 128; ``return_attn_probs`` gives (out, softmax_lse, None))."""
+    if q.dtype == torch.float8_e4m3fn or q_descale is not None or k_descale is not None or v_descale is not None:
+        scale = _fp8_route(q, k, v, q.shape[0], dropout_p, softmax_scale, softcap, alibi_slopes, (q_descale, k_descale, v_descale))
+        out, lse = _flash_attn_fp8_forward(q, k, v, q_descale, k_descale, v_descale, scale, causal, window_size[0], window_size[1])
+        return (out, lse, None) if return_attn_probs else out
     return _AttnFn.apply(q, k, v, dropout_p, softmax_scale, causal, tuple(window_size), softcap, alibi_slopes,
                          deterministic, return_attn_probs, torch.is_grad_enabled())
 
@@ -443,9 +500,19 @@ def flash_attn_qkvpacked_func(qkv, dropout_p=0.0, softmax_scale=None, causal=Fal
 
 def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p=0.0,
                            softmax_scale=None, causal=False, window_size=(-1, -1), softcap=0.0, alibi_slopes=None,
-                           deterministic=False, return_attn_probs=False, block_table=None):
+                           deterministic=False, return_attn_probs=False, block_table=None, *, q_descale=None, k_descale=None,
+                           v_descale=None):
     """q (total_q,H,D); k, v (total_k,Hk,D); cu_seqlens_* int32 (B+1) cumulative lengths on the device.
-    Returns out (total_q,H,D) (and softmax_lse (H,total_q) when ``return_attn_probs``)."""
+    Returns out (total_q,H,D) (and softmax_lse (H,total_q) when ``return_attn_probs``).  float8_e4m3fn inputs: as flash_attn_func
+    (descales (B, Hk) with B = len(cu_seqlens_q) - 1; no block_table)."""
+    if q.dtype == torch.float8_e4m3fn or q_descale is not None or k_descale is not None or v_descale is not None:
+        scale = _fp8_route(q, k, v, cu_seqlens_q.shape[0] - 1, dropout_p, softmax_scale, softcap, alibi_slopes,
+                           (q_descale, k_descale, v_descale))
+        if block_table is not None:
+            raise RuntimeError("the fp8 forward does not support block_table (paged KV)")
+        out, lse = _flash_attn_varlen_fp8_forward(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, q_descale, k_descale,
+                                                  v_descale, scale, causal, window_size[0], window_size[1])
+        return (out, lse, None) if return_attn_probs else out
     return _VarlenAttnFn.apply(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale,
                                causal, tuple(window_size), softcap, alibi_slopes, deterministic, return_attn_probs,
                                block_table, torch.is_grad_enabled())

@@ -45,7 +45,7 @@ extern "C" {
 
 #define FA_ABI_VERSION 6
 
-enum { FA_DTYPE_FP16 = 0, FA_DTYPE_BF16 = 1 };
+enum { FA_DTYPE_FP16 = 0, FA_DTYPE_BF16 = 1, FA_DTYPE_FP8_E4M3 = 2 /* OCP e4m3 (float8_e4m3fn): fa_fwd_fp8 / fa_varlen_fwd_fp8 only */ };
 
 enum {
   FA_OK = 0,
@@ -198,6 +198,17 @@ typedef struct FaBwdParams {
                                    past it are not written */
 } FaBwdParams;
 
+/* Descale factors of the FP8 forward (fa_fwd_fp8 / fa_varlen_fwd_fp8): fp32 device tensors of shape (B, Hk) -- per KV head, FA3's
+ * q_descale / k_descale / v_descale (hopper/flash_api.cpp) -- with any strides (in elements).  A NULL pointer means 1.0. */
+typedef struct FaFp8Params {
+  const float* q_descale;
+  const float* k_descale;
+  const float* v_descale;
+  int64_t q_descale_batch_stride, q_descale_head_stride;
+  int64_t k_descale_batch_stride, k_descale_head_stride;
+  int64_t v_descale_batch_stride, v_descale_head_stride;
+} FaFp8Params;
+
 /* ABI version of the loaded library (== FA_ABI_VERSION of the header it was built from). */
 int fa_abi_version(void);
 /* sizeof() of the two parameter blocks as the library sees them (binder self-check). */
@@ -205,6 +216,7 @@ int fa_sizeof_fwd_params(void);
 int fa_sizeof_bwd_params(void);
 int fa_sizeof_kvappend_params(void);
 int fa_sizeof_rotary_params(void);
+int fa_sizeof_fp8_params(void);
 /* Last error message of the calling thread ("" if none). */
 const char* fa_last_error(void);
 
@@ -214,7 +226,7 @@ void fa_knobs_reload(void);
 /* Which kernels the calling thread's last fa_fwd* / fa_bwd* call enqueued (for tests and the benchmark's labels; the
  * reference exposes nothing comparable -- its dispatch is compile-time, flash_fwd_launch_template.h).  Fills up to n of
  * FA_SCHEDULE_FIELDS int32: {forward kernel id (0 none, 1 lock-step fa_fwd_kernel, 2 pipelined fa_fwd_il_kernel,
- * 3 64-rows-per-wave fa_fwd_w64_kernel), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
+ * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
  * varlen work list used, head dim, bf16, dQ-kernel waves, backward work lists used, backward spilled dS (5 contractions),
  * query heads packed into the rows of a block (fa_fwd_kvcache, 1 = none), dK/dV schedule (8 waves x 32 keys, 4 at head dim 256,
  * or 64 = 4 waves x 64 keys)}; returns FA_SCHEDULE_FIELDS (fields are only ever appended). */
@@ -241,6 +253,14 @@ int fa_bwd_plan_query(const FaBwdParams* params, int32_t* out, int n);
 int fa_fwd(const FaFwdParams* params, void* stream);
 /* Forward, packed variable-length batch.  cu_seqlens_q/k must be non-NULL device int32 (b+1). */
 int fa_varlen_fwd(const FaFwdParams* params, void* stream);
+/* Forward on FP8 inputs (FA3's fp8 forward): q / k / v are OCP e4m3 (dtype FA_DTYPE_FP8_E4M3; strides multiples of 16 bytes, pointers 16-byte
+ * aligned), o is bf16 (strides multiples of 8 elements).  S = softmax_scale * q_descale * k_descale * q.k^T on the exact fp8 values, P = softmax(S)
+ * rounded to e4m3, o = P.(v_descale * v); softmax_lse as fa_fwd.  fp8 may be NULL (all descales 1).  Causal / window masks, MHA / GQA / MQA,
+ * head dims 64 and 128.  FA_ERR_UNSUPPORTED (with a message naming it) for any other head dim, softcap, ALiBi, dropout, return_softmax,
+ * seqused_q / seqused_k, leftpad_k, block_table and the KV-cache arguments; there is no fp8 KV-cache entry point and no fp8 backward.
+ * fa_varlen_fwd_fp8: packed batch as fa_varlen_fwd (the workspace of fa_fwd_workspace_bytes holds the work list of an uneven batch). */
+int fa_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
+int fa_varlen_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
 /* Inference forward against a KV cache: fa_fwd plus seqused_k (cache_seqlens), cache_batch_idx and/or a
  * paged cache (block_table).  k/v point at the cache.  No backward. */
 int fa_fwd_kvcache(const FaFwdParams* params, void* stream);

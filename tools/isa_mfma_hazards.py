@@ -35,14 +35,19 @@ def disassemble(obj):
         return subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", co], text=True)
 
 
-def passes_of(op):
+def passes_of(op, operands=""):
     m = re.match(r"v_mfma_\w+?_(\d+)x(\d+)x(\d+)_?(\w*)", op)
     if not m:
         return 16
     mm, _, kk, ty = int(m.group(1)), int(m.group(2)), int(m.group(3)), m.group(4)
     if ty in ("bf16", "f16"):   # gfx950: 32x32x16 = 8 passes, 16x16x32 = 4; the half-K forms of gfx942 take as long for half the work
         return 8 if mm == 32 else 4
-    if ty.startswith(("f8", "bf8", "fp8")) or "f8f6f4" in op:
+    if "f8f6f4" in op:   # block-scaled (MI355X_MICROARCH.md, matrix cores): an fp8 / bf8 operand (cbsz / blgp 0, 1) takes twice the cycles of the bf16 form
+        fmt = [int(f.group(1)) if f else 0 for f in (re.search(r"cbsz:(\d+)", operands), re.search(r"blgp:(\d+)", operands))]
+        if min(fmt) <= 1:   # 32x32x64 = 16 passes, 16x16x128 = 8
+            return 16 if mm == 32 else 8
+        return 8 if mm == 32 else 4   # fp6 / fp4 operands: the cycles of the bf16 form
+    if ty.startswith(("f8", "bf8", "fp8")):   # non-scaled fp8 (32x32x16, 16x16x32): the bf16 rate
         return 8 if mm == 32 else 4
     return 16 if mm == 32 else 8    # f32 / xf32 / f64 / i8: priced at the slow end (none in the hot kernels)
 
@@ -107,7 +112,7 @@ def scan(text):
         op, rest, _ = ins[i]
         line = f"{op} {rest}"
         if op.startswith(("v_mfma", "v_smfmac")):
-            p = passes_of(op)
+            p = passes_of(op, rest)
             dst = regs_of(rest.split(",")[0])
             touched = regs_of(rest.split(",", 1)[1] if "," in rest else "")
             keep = []
