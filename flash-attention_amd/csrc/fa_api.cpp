@@ -61,6 +61,8 @@ const fa::Knobs* read_knobs() {
   k->dkdv_prescale = env_int("FA_DKDV_PRESCALE", 0);
   k->bwd_fuse_delta = env_int("FA_BWD_FUSE_DELTA", 1);
   k->pack_gqa = env_int("FA_PACK_GQA", 1);
+  k->fp8_kv_ring = env_int("FA_FP8_KV_RING", 4);
+  if (k->fp8_kv_ring < 2 || k->fp8_kv_ring > 4) k->fp8_kv_ring = 4;
   if (k->strict) k->rescale_thr = 0.f;
   return k;
 }
@@ -864,6 +866,98 @@ int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool va
   return FA_OK;
 }
 
+// FP8 forward against an fp8 KV cache (fa_fwd_fp8_kv.hip): the decode side of do_fwd_fp8.  cache_seqlens (seqused_k + seqused_k_add), cache_batch_idx, a paged
+// cache, causal / window masks, head packing and split keys as fa_fwd_kvcache; everything else is refused here, before any launch.
+int do_fwd_kvcache_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream) {
+  if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
+  g_err[0] = 0;
+  const char* fn = "fa_fwd_kvcache_fp8";
+  if (a->dtype != FA_DTYPE_FP8_E4M3)
+    return fail(FA_ERR_INVALID_ARGUMENT, "%s takes FA_DTYPE_FP8_E4M3 (float8_e4m3fn) q and k / v caches, got dtype %d", fn, a->dtype);
+  if (a->b <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "batch size must be positive");
+  if (a->h <= 0 || a->h_k <= 0 || a->h % a->h_k != 0)
+    return fail(FA_ERR_INVALID_ARGUMENT, "Number of heads in key/value must divide number of heads in query");
+  if (a->d != 64 && a->d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
+  if (a->softcap < 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "softcap must be non-negative");
+  if (a->softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: softcap is not supported on the fp8 path", fn);
+  if (a->alibi_slopes) return fail(FA_ERR_UNSUPPORTED, "%s: ALiBi is not supported on the fp8 path", fn);
+  if (a->p_dropout != 0.f || a->rng_state || a->randval) return fail(FA_ERR_UNSUPPORTED, "%s: dropout / return_softmax are not supported on the fp8 path", fn);
+  if (a->leftpad_k) return fail(FA_ERR_UNSUPPORTED, "%s: leftpad_k (cache_leftpad) is not supported on the fp8 path", fn);
+  if (a->seqused_q) return fail(FA_ERR_UNSUPPORTED, "%s: seqused_q is not supported on the fp8 path", fn);
+  if (a->cu_seqlens_q || a->cu_seqlens_k) return fail(FA_ERR_INVALID_ARGUMENT, "%s takes fixed-length batches (cu_seqlens must be NULL)", fn);
+  if (!a->q || !a->k || !a->v || !a->o || !a->softmax_lse)
+    return fail(FA_ERR_INVALID_ARGUMENT, "q, k, v, o and softmax_lse must be non-NULL");
+  if (a->seqlen_q < 0 || a->seqlen_k < 0 || a->seqused_k_add < 0) return fail(FA_ERR_INVALID_ARGUMENT, "negative sequence length");
+  if (a->num_splits < 0) return fail(FA_ERR_INVALID_ARGUMENT, "num_splits must be >= 0");
+  if (a->block_table) {
+    if (a->cache_batch_idx) return fail(FA_ERR_INVALID_ARGUMENT, "Paged KVcache does not support cache_batch_idx");
+    if (a->page_block_size <= 0 || a->page_block_size % 256 != 0)
+      return fail(FA_ERR_INVALID_ARGUMENT, "Paged KV cache block size must be divisible by 256");
+    if (a->seqlen_k <= 0 || a->seqlen_k % a->page_block_size != 0)
+      return fail(FA_ERR_INVALID_ARGUMENT, "%s: with block_table, seqlen_k is max_num_blocks_per_seq * page_block_size (at least one page)", fn);
+  }
+  // 16-byte DMA pieces and stores: e4m3 rows start on 16 bytes, bf16 rows of o on 8 elements
+  auto al16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  if (!al16(a->q) || !al16(a->k) || !al16(a->v) || !al16(a->o)) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q, k, v and o must be 16-byte aligned", fn);
+  const int64_t in_strides[] = {a->q_row_stride, a->q_head_stride, a->q_batch_stride, a->k_row_stride, a->k_head_stride, a->k_batch_stride,
+                                a->v_row_stride, a->v_head_stride, a->v_batch_stride};
+  for (int64_t s : in_strides)
+    if (s % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: q / k / v strides must be multiples of 16 bytes", fn);
+  const int64_t o_strides[] = {a->o_row_stride, a->o_head_stride, a->o_batch_stride};
+  for (int64_t s : o_strides)
+    if (s % 8 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: o (bf16) strides must be multiples of 8 elements", fn);
+  if (a->seqlen_q == 0 || a->total_q == 0) return FA_OK;  // nothing to write
+
+  fa::FwdK k{};
+  k.n_splits = 1;
+  k.pack_g = 1;
+  k.q = a->q; k.k = a->k; k.v = a->v; k.o = a->o; k.lse = a->softmax_lse;
+  k.q_bs = a->q_batch_stride; k.q_rs = a->q_row_stride; k.q_hs = a->q_head_stride;
+  k.k_bs = a->k_batch_stride; k.k_rs = a->k_row_stride; k.k_hs = a->k_head_stride;
+  k.v_bs = a->v_batch_stride; k.v_rs = a->v_row_stride; k.v_hs = a->v_head_stride;
+  k.o_bs = a->o_batch_stride; k.o_rs = a->o_row_stride; k.o_hs = a->o_head_stride;
+  k.seqused_k = a->seqused_k; k.seqused_add = a->seqused_k_add;
+  k.kv_batch_idx = a->cache_batch_idx; k.block_table = a->block_table; k.block_table_bs = a->block_table_batch_stride;
+  k.page_size = a->page_block_size;
+  k.b = a->b; k.h = a->h; k.h_k = a->h_k; k.hk_ratio = a->h / a->h_k;
+  k.sq = a->seqlen_q; k.sk = a->seqlen_k; k.total_q = a->total_q;
+  int causal = a->is_causal, wl = a->window_left, wr = a->window_right;
+  normalize_window(a->seqlen_q, a->seqlen_k, false, causal, wl, wr);
+  k.wl = wl; k.wr = wr;
+  k.scale = a->softmax_scale;
+  k.scale_log2 = a->softmax_scale * 1.4426950408889634f;
+  k.rescale_thr = std::min(fa::knobs().rescale_thr, 8.f);  // P is rounded to e4m3: P <= 2^8 < 448 (do_fwd_fp8)
+  const int pack = pack_group(a);
+  if (pack > 1) { k.pack_g = pack; k.h = a->h_k; k.hk_ratio = 1; k.sq = a->seqlen_q * pack; }
+  int split_tiles = 0;
+  const int ns = choose_splits(a, split_tiles);
+  if (ns > 1) {
+    const int64_t need = splitkv_bytes(a, ns);
+    if (a->workspace && a->workspace_bytes >= need) {
+      k.n_splits = ns; k.split_tiles = split_tiles;
+      k.o_accum = (float*)a->workspace;
+      k.lse_accum = k.o_accum + (int64_t)ns * a->b * a->h * a->seqlen_q * head_dim_pitch(a->d);
+    } else if (a->num_splits > 1) {
+      return fail(FA_ERR_WORKSPACE, "%s: num_splits = %d needs a workspace of %lld bytes (fa_fwd_workspace_bytes)", fn, a->num_splits, (long long)need);
+    }  // auto schedule without a workspace: run unsplit
+  }
+  constexpr int bm = 128;
+  k.nmb = (k.sq + bm - 1) / bm;
+  fa::choose_units(a->b, a->h_k, k.hk_ratio, k.nmb * k.n_splits, k.n_units, k.unit_size, k.unit_hpx);
+  fa::Fp8K f8{};
+  if (f) {
+    f8.q_descale = f->q_descale; f8.q_bs = f->q_descale_batch_stride; f8.q_hs = f->q_descale_head_stride;
+    f8.k_descale = f->k_descale; f8.k_bs = f->k_descale_batch_stride; f8.k_hs = f->k_descale_head_stride;
+    f8.v_descale = f->v_descale; f8.v_bs = f->v_descale_batch_stride; f8.v_hs = f->v_descale_head_stride;
+  }
+  int rc = fa::launch_fwd_fp8_kv(k, f8, a->d, (hipStream_t)stream);
+  if (rc == 0 && k.n_splits > 1) rc = fa::launch_splitkv_combine(k, 1, a->d, (hipStream_t)stream);   // (the partials are fp32, o is bf16)
+  if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
+  if (rc == -3) return fail(FA_ERR_UNSUPPORTED, "k/v row stride too large: one 64-key tile (64 * row_stride bytes) must span less than 2 GiB");
+  if (rc != 0) return fail(FA_ERR_LAUNCH, "forward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+  return FA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -872,6 +966,7 @@ int fa_abi_version(void) { return FA_ABI_VERSION; }
 int fa_sizeof_fp8_params(void) { return (int)sizeof(FaFp8Params); }
 int fa_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream) { return do_fwd_fp8(params, fp8, stream, false); }
 int fa_varlen_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream) { return do_fwd_fp8(params, fp8, stream, true); }
+int fa_fwd_kvcache_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream) { return do_fwd_kvcache_fp8(params, fp8, stream); }
 int fa_sizeof_fwd_params(void) { return (int)sizeof(FaFwdParams); }
 int fa_sizeof_bwd_params(void) { return (int)sizeof(FaBwdParams); }
 int fa_sizeof_kvappend_params(void) { return (int)sizeof(FaKvAppendParams); }
@@ -930,10 +1025,20 @@ int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (!a->knew || !a->vnew || !a->kcache || !a->vcache) return fail(FA_ERR_INVALID_ARGUMENT, "knew, vnew, kcache and vcache must be non-NULL");
-  if (a->d <= 0 || a->d % 8 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "head dimension must be a multiple of 8");
-  if (a->dtype != FA_DTYPE_FP16 && a->dtype != FA_DTYPE_BF16) return fail(FA_ERR_INVALID_ARGUMENT, "FlashAttention only supports fp16 and bf16 data type");
+  const bool fp8 = a->dtype == FA_DTYPE_FP8_E4M3;   // one byte per element: the copy kernel moves 16-byte chunks of 16-bit words, so the row is d / 2 words
+  if (a->d <= 0 || a->d % (fp8 ? 16 : 8) != 0) return fail(FA_ERR_INVALID_ARGUMENT, fp8 ? "fa_kvcache_append: the head dimension of an e4m3 cache must be a multiple of 16" : "head dimension must be a multiple of 8");
+  if (a->dtype != FA_DTYPE_FP16 && a->dtype != FA_DTYPE_BF16 && !fp8) return fail(FA_ERR_INVALID_ARGUMENT, "FlashAttention only supports fp16 and bf16 data type");
   if (a->block_table && (a->page_block_size <= 0 || a->page_block_size % 256 != 0))
     return fail(FA_ERR_INVALID_ARGUMENT, "Paged KV cache block size must be divisible by 256");
+  if (fp8) {
+    if (a->block_table && a->cache_batch_idx) return fail(FA_ERR_INVALID_ARGUMENT, "Paged KVcache does not support cache_batch_idx");
+    if ((((uintptr_t)a->knew | (uintptr_t)a->vnew | (uintptr_t)a->kcache | (uintptr_t)a->vcache) & 15u) != 0)
+      return fail(FA_ERR_INVALID_ARGUMENT, "fa_kvcache_append: e4m3 knew, vnew, kcache and vcache must be 16-byte aligned");
+    const int64_t strides[] = {a->knew_batch_stride, a->knew_row_stride, a->knew_head_stride, a->vnew_batch_stride, a->vnew_row_stride, a->vnew_head_stride,
+                               a->kcache_batch_stride, a->kcache_row_stride, a->kcache_head_stride, a->vcache_batch_stride, a->vcache_row_stride, a->vcache_head_stride};
+    for (int64_t st : strides)
+      if (st % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "fa_kvcache_append: e4m3 strides must be multiples of 16 bytes");
+  }
   fa::KvAppendK k{};
   k.knew = a->knew; k.vnew = a->vnew; k.kcache = a->kcache; k.vcache = a->vcache;
   k.kn_bs = a->knew_batch_stride; k.kn_rs = a->knew_row_stride; k.kn_hs = a->knew_head_stride;
@@ -943,6 +1048,10 @@ int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
   k.seqlens_k = a->seqlens_k; k.kv_batch_idx = a->cache_batch_idx; k.block_table = a->block_table;
   k.block_table_bs = a->block_table_batch_stride; k.page_size = a->page_block_size;
   k.b = a->b; k.s_new = a->seqlen_new; k.h_k = a->h_k; k.d = a->d;
+  if (fp8) {   // bytes -> 16-bit words (a byte copy: nothing is requantised)
+    k.d /= 2;
+    for (int64_t* st : {&k.kn_bs, &k.kn_rs, &k.kn_hs, &k.vn_bs, &k.vn_rs, &k.vn_hs, &k.kc_bs, &k.kc_rs, &k.kc_hs, &k.vc_bs, &k.vc_rs, &k.vc_hs}) *st /= 2;
+  }
   if (fa::launch_kv_append(k, (hipStream_t)stream) != 0)
     return fail(FA_ERR_LAUNCH, "kv append launch failed: %s", hipGetErrorString(hipGetLastError()));
   return FA_OK;
@@ -952,6 +1061,7 @@ int fa_rotary(const FaRotaryParams* a, void* stream) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (!a->x || !a->y || !a->cos || !a->sin) return fail(FA_ERR_INVALID_ARGUMENT, "x, y, cos and sin must be non-NULL");
+  if (a->dtype == FA_DTYPE_FP8_E4M3) return fail(FA_ERR_UNSUPPORTED, "fa_rotary: rotary on float8_e4m3fn values needs a requantisation that is not defined (rotate before quantising)");
   if (a->dtype != FA_DTYPE_FP16 && a->dtype != FA_DTYPE_BF16) return fail(FA_ERR_INVALID_ARGUMENT, "FlashAttention only supports fp16 and bf16 data type");
   if (a->d <= 0 || a->d % 8 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "head dimension must be a multiple of 8");
   if (a->rotary_dim <= 0 || a->rotary_dim > a->d) return fail(FA_ERR_INVALID_ARGUMENT, "rotary_dim must be <= headdim");

@@ -31,6 +31,7 @@ struct Knobs {
   int dkdv_prescale;   // FA_DKDV_PRESCALE=1: the plain dK/dV kernel pre-scales K by softmax_scale*log2e (rounded to the input dtype; ~3 % faster, fa_bwd.hip: PRE);
                        // default 0 = every score scaled in fp32 (FEAT_EXACT)
   int bwd_fuse_delta;  // FA_BWD_FUSE_DELTA=0: always run the delta pre-pass (default 1: the 64-rows-per-wave dQ kernel computes softmax_d of its rows itself and runs first)
+  int fp8_kv_ring;     // FA_FP8_KV_RING: K / V staging slots of the fp8 KV-cache forward (fa_fwd_fp8_kv.hip; the LDS-DMA runs one tile less ahead): 2, 3 or 4 (default 4)
   int strict;          // FA_STRICT=1: the reference's numerics contract -- rescale on any growth of a row maximum (threshold 0) and
                        // softmax_scale applied in fp32 to every score (never the bf16 pre-scaled Q of the 64-rows-per-wave kernel)
 };
@@ -38,7 +39,7 @@ const Knobs& knobs();
 
 // What the last fa_fwd* / fa_bwd* call of this thread launched (fa_last_schedule in the C ABI).
 struct LastSchedule {
-  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel
+  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel, 5 fa_fwd_fp8_kv_kernel
   int fwd_nw;       // waves per workgroup (16 = 8-wave ping-pong)
   int fwd_feat;     // FEAT_* variant of the lock-step kernel
   int fwd_splits;   // split-KV factor
@@ -132,6 +133,9 @@ int launch_fwd_w64(const FwdK& p, int dtype_bf16, int d, hipStream_t stream);
 // FP8 (e4m3) forward (fa_fwd_fp8.hip): 4 waves, 128 query rows per workgroup, head dims 64 / 128, bf16 o.  -2 = head dim not built,
 // -3 = one 64-key tile spans >= 2 GiB.
 int launch_fwd_fp8(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
+// FP8 (e4m3) forward against an fp8 KV cache (fa_fwd_fp8_kv.hip): seqused_k / kv_batch_idx / block_table / pack_g / n_splits of FwdK as the lock-step
+// kernel reads them; with n_splits > 1 the caller runs launch_splitkv_combine (bf16) behind it.  Same return codes.
+int launch_fwd_fp8_kv(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
 
 // Backward: delta = rowsum(dO*O) pre-pass, dK/dV kernel (loops over query blocks),
 // dQ kernel (loops over key blocks).  Same return convention.

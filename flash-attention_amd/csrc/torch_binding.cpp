@@ -608,7 +608,7 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
 }
 
 // ---- FP8 forward (FA3's fp8 contract, hopper/flash_api.cpp:694-696 and :859-863): float8_e4m3fn q / k / v, optional fp32 (B, Hk) descales with any
-// strides, bf16 out.  Two names beyond the reference's five (fwd_fp8 / varlen_fwd_fp8), so that its positional orders stay untouched.
+// strides, bf16 out.  Names beyond the reference's five (fwd_fp8 / varlen_fwd_fp8, and fwd_kvcache_fp8 below), so that its positional orders stay untouched.
 void fp8_checks(const Tensor& q, const Tensor& k, const Tensor& v) {
   CHECK_DEVICE(q); CHECK_DEVICE(k); CHECK_DEVICE(v);
   TORCH_CHECK(q.dtype() == at::kFloat8_e4m3fn && k.dtype() == at::kFloat8_e4m3fn && v.dtype() == at::kFloat8_e4m3fn,
@@ -715,6 +715,114 @@ std::vector<Tensor> mha_varlen_fwd_fp8(const Tensor& q, const Tensor& k, const T
   return {out, lse};
 }
 
+// FP8 forward against an fp8 KV cache (FA3's flash_attn_with_kvcache with q_descale / k_descale / v_descale; C ABI fa_kvcache_append + fa_fwd_kvcache_fp8).
+// A name of its own, like fwd_fp8: the reference's fwd_kvcache keeps its positional order.  The append is a byte copy -- the caller quantises new keys /
+// values with the cache's scale; rotary, leftpad, ALiBi and softcap have no slot here (the Python wrapper refuses them by name).
+std::vector<Tensor> mha_fwd_kvcache_fp8(const Tensor& q, const Tensor& kcache, const Tensor& vcache, OptTensor& k_, OptTensor& v_, OptTensor& seqlens_k_,
+                                        OptTensor& cache_batch_idx_, OptTensor& block_table_, OptTensor& out_, const OptTensor& q_descale,
+                                        const OptTensor& k_descale, const OptTensor& v_descale, const double softmax_scale, bool is_causal,
+                                        int64_t window_size_left, int64_t window_size_right, int64_t num_splits) {
+  CHECK_DEVICE(q); CHECK_DEVICE(kcache); CHECK_DEVICE(vcache);
+  TORCH_CHECK(q.dtype() == at::kFloat8_e4m3fn && kcache.dtype() == at::kFloat8_e4m3fn && vcache.dtype() == at::kFloat8_e4m3fn,
+              "fwd_kvcache_fp8: q, kcache and vcache must have dtype torch.float8_e4m3fn (mixed dtypes -- bf16 q against an fp8 cache -- are not supported)");
+  TORCH_CHECK(q.dim() == 4 && kcache.dim() == 4 && vcache.dim() == 4 && q.stride(-1) == 1 && kcache.stride(-1) == 1 && vcache.stride(-1) == 1,
+              "Input tensor must be 4-D with contiguous last dimension");
+  const bool paged = block_table_.has_value();
+  if (paged) {
+    TORCH_CHECK(!cache_batch_idx_.has_value(), "Paged KVcache does not support cache_batch_idx");
+    CHECK_DEVICE(*block_table_);
+    TORCH_CHECK(block_table_->dtype() == at::kInt && block_table_->dim() == 2 && block_table_->stride(-1) == 1,
+                "block_table must be a 2-D int32 tensor with a contiguous last dimension");
+  }
+  const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
+  const int64_t Hk = kcache.size(2);
+  const int64_t page = paged ? kcache.size(1) : 0;
+  const int64_t Sk = paged ? block_table_->size(1) * page : kcache.size(1);
+  TORCH_CHECK(B > 0, "batch size must be positive");
+  TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  TORCH_CHECK(kcache.size(3) == D && vcache.sizes() == kcache.sizes(), "kcache / vcache shape mismatch");
+  if (paged) {
+    TORCH_CHECK(page % 256 == 0, "Paged KV cache block size must be divisible by 256");
+    TORCH_CHECK(block_table_->size(0) == B, "block_table must have shape (batch_size, max_num_blocks_per_seq)");
+  } else if (!cache_batch_idx_.has_value()) {
+    TORCH_CHECK(kcache.size(0) == B, "kcache batch size must match q (or pass cache_batch_idx)");
+  }
+  if (seqlens_k_.has_value()) {
+    CHECK_DEVICE(*seqlens_k_);
+    TORCH_CHECK(seqlens_k_->dtype() == at::kInt && seqlens_k_->is_contiguous() && seqlens_k_->sizes() == at::IntArrayRef({B}),
+                "seqlens_k must be a contiguous int32 tensor of shape (batch_size)");
+  }
+  if (cache_batch_idx_.has_value()) {
+    CHECK_DEVICE(*cache_batch_idx_);
+    TORCH_CHECK(cache_batch_idx_->dtype() == at::kInt && cache_batch_idx_->is_contiguous() && cache_batch_idx_->sizes() == at::IntArrayRef({B}),
+                "cache_batch_idx must be a contiguous int32 tensor of shape (batch_size)");
+  }
+  c10::DeviceGuard guard(q.device());
+  const int64_t s_new = k_.has_value() ? k_->size(1) : 0;
+  TORCH_CHECK(s_new <= Sk, "If key is supplied, it must have seqlen <= the seqlen of the KV cache");
+  if (paged && seqlens_k_.has_value()) {  // the reference's guard (flash_api.cpp:1433-1447); costs a device->host sync
+    const int64_t need = seqlens_k_->max().item<int>() + s_new;
+    TORCH_CHECK(need <= Sk, "Paged KV cache: max(seqlens_k)", s_new > 0 ? " + seqlen_knew" : "", " (= ", need,
+                ") exceeds the capacity addressable by block_table (max_num_blocks_per_seq * page_block_size = ", Sk, ")");
+  }
+  FaFp8Params f{};
+  fp8_descale(f, 0, q_descale, B, Hk); fp8_descale(f, 1, k_descale, B, Hk); fp8_descale(f, 2, v_descale, B, Hk);
+  Tensor out = fp8_out(out_, q, {B, Sq, H, D});
+  Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  if (Sq == 1) { is_causal = false; window_size_right = -1; }  // one bottom-right aligned query row sees every key
+  if (k_.has_value()) {
+    TORCH_CHECK(v_.has_value() && seqlens_k_.has_value(), "If key is supplied, value and seqlens_k must also be passed in");
+    const Tensor &kn = *k_, &vn = *v_;
+    CHECK_DEVICE(kn); CHECK_DEVICE(vn);
+    TORCH_CHECK(kn.dtype() == at::kFloat8_e4m3fn && vn.dtype() == at::kFloat8_e4m3fn && kn.stride(-1) == 1 && vn.stride(-1) == 1 &&
+                kn.sizes() == at::IntArrayRef({B, s_new, Hk, D}) && vn.sizes() == kn.sizes(),
+                "new key / value must be float8_e4m3fn of shape (batch_size, seqlen_new, num_heads_k, head_size) with a contiguous last dimension");
+    FaKvAppendParams ap{};
+    ap.knew = kn.data_ptr(); ap.vnew = vn.data_ptr(); ap.kcache = kcache.data_ptr(); ap.vcache = vcache.data_ptr();
+    ap.knew_batch_stride = kn.stride(0); ap.knew_row_stride = kn.stride(1); ap.knew_head_stride = kn.stride(2);
+    ap.vnew_batch_stride = vn.stride(0); ap.vnew_row_stride = vn.stride(1); ap.vnew_head_stride = vn.stride(2);
+    ap.kcache_batch_stride = kcache.stride(0); ap.kcache_row_stride = kcache.stride(1); ap.kcache_head_stride = kcache.stride(2);
+    ap.vcache_batch_stride = vcache.stride(0); ap.vcache_row_stride = vcache.stride(1); ap.vcache_head_stride = vcache.stride(2);
+    ap.seqlens_k = seqlens_k_->data_ptr<int>();
+    ap.cache_batch_idx = cache_batch_idx_.has_value() ? cache_batch_idx_->data_ptr<int>() : nullptr;
+    ap.block_table = paged ? block_table_->data_ptr<int>() : nullptr;
+    ap.block_table_batch_stride = paged ? block_table_->stride(0) : 0;
+    ap.page_block_size = (int)page;
+    ap.b = B; ap.seqlen_new = (int)s_new; ap.h_k = Hk; ap.d = D; ap.dtype = FA_DTYPE_FP8_E4M3;
+    if (s_new > 0) fa_check(fa_kvcache_append(&ap, cur_stream(q)));
+  }
+  if (Sk == 0) {
+    out.zero_();
+    lse.fill_(std::numeric_limits<float>::infinity());
+  } else if (Sq > 0) {
+    FaFwdParams a{};
+    a.q = q.data_ptr(); a.k = kcache.data_ptr(); a.v = vcache.data_ptr(); a.o = out.data_ptr(); a.softmax_lse = lse.data_ptr<float>();
+    a.q_batch_stride = q.stride(0); a.q_row_stride = q.stride(1); a.q_head_stride = q.stride(2);
+    a.k_batch_stride = kcache.stride(0); a.k_row_stride = kcache.stride(1); a.k_head_stride = kcache.stride(2);
+    a.v_batch_stride = vcache.stride(0); a.v_row_stride = vcache.stride(1); a.v_head_stride = vcache.stride(2);
+    a.o_batch_stride = out.stride(0); a.o_row_stride = out.stride(1); a.o_head_stride = out.stride(2);
+    a.seqused_k = seqlens_k_.has_value() ? seqlens_k_->data_ptr<int>() : nullptr;
+    a.seqused_k_add = (int)s_new;
+    a.cache_batch_idx = cache_batch_idx_.has_value() ? cache_batch_idx_->data_ptr<int>() : nullptr;
+    a.block_table = paged ? block_table_->data_ptr<int>() : nullptr;
+    a.block_table_batch_stride = paged ? block_table_->stride(0) : 0;
+    a.page_block_size = (int)page;
+    a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = (int)Sq; a.seqlen_k = (int)Sk; a.total_q = B * Sq;
+    a.dtype = FA_DTYPE_FP8_E4M3;
+    a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
+    a.softmax_scale = (float)softmax_scale;
+    a.num_splits = (int)num_splits;
+    Tensor ws;  // split-KV partials, freed in stream order
+    const int64_t ws_bytes = fa_fwd_workspace_bytes(&a);
+    if (ws_bytes > 0) {
+      ws = at::empty({ws_bytes}, q.options().dtype(at::kByte));
+      a.workspace = ws.data_ptr(); a.workspace_bytes = ws_bytes;
+    }
+    fa_check(fa_fwd_kvcache_fp8(&a, &f, cur_stream(q)));
+  }
+  return {out, lse};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -730,5 +838,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("varlen_bwd", &mha_varlen_bwd, "Backward pass (variable length)");
   m.def("fwd_kvcache", &mha_fwd_kvcache, "Forward pass, with KV-cache");
   m.def("fwd_fp8", &mha_fwd_fp8, "Forward pass, FP8 (e4m3) inputs with per-(batch, kv head) descales, bf16 output");
+  m.def("fwd_kvcache_fp8", &mha_fwd_kvcache_fp8, "Forward pass against an FP8 (e4m3) KV cache, FP8 queries, per-(batch, kv head) descales, bf16 output");
   m.def("varlen_fwd_fp8", &mha_varlen_fwd_fp8, "Forward pass (variable length), FP8 (e4m3) inputs with per-(batch, kv head) descales, bf16 output");
 }

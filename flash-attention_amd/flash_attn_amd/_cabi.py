@@ -98,7 +98,7 @@ EXPORTS = (
     "fa_last_error", "fa_rotary", "fa_knobs_reload", "fa_last_schedule", "fa_last_kernel_name", "fa_fwd_schedule_query", "fa_bwd_dq_schedule_query", "fa_bwd_plan_query",
     "fa_fwd", "fa_varlen_fwd", "fa_fwd_kvcache", "fa_kvcache_append", "fa_set_rng_state", "fa_fwd_workspace_bytes",
     "fa_bwd_workspace_bytes", "fa_bwd", "fa_varlen_bwd", "fa_bwd_fused_status",
-    "fa_sizeof_fp8_params", "fa_fwd_fp8", "fa_varlen_fwd_fp8",
+    "fa_sizeof_fp8_params", "fa_fwd_fp8", "fa_varlen_fwd_fp8", "fa_fwd_kvcache_fp8",
 )
 
 _LIB = None
@@ -140,7 +140,7 @@ def load():
         fn.restype = C.c_int
     lib.fa_sizeof_rotary_params.restype = C.c_int
     lib.fa_sizeof_fp8_params.restype = C.c_int
-    for fn in (lib.fa_fwd_fp8, lib.fa_varlen_fwd_fp8):
+    for fn in (lib.fa_fwd_fp8, lib.fa_varlen_fwd_fp8, lib.fa_fwd_kvcache_fp8):
         fn.argtypes = [C.POINTER(FaFwdParams), C.POINTER(FaFp8Params), C.c_void_p]
         fn.restype = C.c_int
     lib.fa_knobs_reload.argtypes = []

@@ -1,6 +1,6 @@
 """Backend-module API of the reference (``flash_attn_2_cuda``) on top of the C ABI, via ctypes.
 
-Exports ``fwd``, ``varlen_fwd``, ``bwd``, ``varlen_bwd`` (and a raising ``fwd_kvcache``) with the
+Exports ``fwd``, ``varlen_fwd``, ``bwd``, ``varlen_bwd`` and ``fwd_kvcache`` (plus the fp8 entries ``fwd_fp8``, ``varlen_fwd_fp8``, ``fwd_kvcache_fp8``) with the
 exact positional signatures the reference custom ops use
 (flash_attn/flash_attn_interface.py:99,177,280,380; C++ originals csrc/flash_attn/flash_api.cpp
 :368-382, :538-561, :800-820, :1010-1035).  Validation messages follow the reference's
@@ -26,7 +26,7 @@ def reload_knobs() -> None:
 
 
 _SCHED_FIELDS = ("fwd_kernel", "fwd_nw", "fwd_feat", "fwd_splits", "fwd_list", "d", "bf16", "bwd_dq_nw", "bwd_list", "bwd_spill", "fwd_pack", "bwd_dkdv_nw")
-FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel"}
+FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel", 5: "fa_fwd_fp8_kv_kernel"}
 
 
 def last_schedule() -> dict:
@@ -675,4 +675,102 @@ def fwd_kvcache(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
             out_.copy_(o2)
             o2 = out_
         out, lse = o2, lse.reshape(B, H, 1)
+    return [out, lse]
+
+
+def fwd_kvcache_fp8(q, kcache, vcache, k_, v_, seqlens_k_, cache_batch_idx_, block_table_, out_, q_descale, k_descale, v_descale,
+                    softmax_scale, is_causal, window_size_left, window_size_right, num_splits) -> List[torch.Tensor]:
+    """FP8 forward against an fp8 KV cache (C ABI fa_kvcache_append + fa_fwd_kvcache_fp8; FA3's flash_attn_with_kvcache with descales):
+    q (B,Sq,H,D), caches (Bc,Sk,Hk,D) or paged (num_blocks,page,Hk,D), optional new k / v (B,S_new,Hk,D), all float8_e4m3fn; optional fp32
+    (B,Hk) descales indexed by the batch entry of q -> [out bf16, softmax_lse].  The append is a byte copy: the caller quantises new keys /
+    values with the cache's scale."""
+    _check_dev(q, kcache, vcache, k_, v_, seqlens_k_, cache_batch_idx_, block_table_)
+    fp8 = torch.float8_e4m3fn
+    if not (q.dtype == kcache.dtype == vcache.dtype == fp8):
+        raise RuntimeError("fwd_kvcache_fp8: q, kcache and vcache must have dtype torch.float8_e4m3fn (mixed dtypes -- bf16 q against an fp8 "
+                           "cache -- are not supported)")
+    for t in (q, kcache, vcache):
+        if t.dim() != 4 or t.stride(-1) != 1:
+            raise RuntimeError("Input tensor must be 4-D with contiguous last dimension")
+    paged = block_table_ is not None
+    if paged:
+        if cache_batch_idx_ is not None:
+            raise RuntimeError("Paged KVcache does not support cache_batch_idx")
+        if block_table_.dtype != torch.int32 or block_table_.dim() != 2 or block_table_.stride(-1) != 1:
+            raise RuntimeError("block_table must be a 2-D int32 tensor with a contiguous last dimension")
+    B, Sq, H, D = q.shape
+    Hk = kcache.shape[2]
+    page = kcache.shape[1] if paged else 0
+    Sk = block_table_.shape[1] * page if paged else kcache.shape[1]
+    if B <= 0:
+        raise RuntimeError("batch size must be positive")
+    if H % Hk != 0:
+        raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    if kcache.shape[3] != D or tuple(vcache.shape) != tuple(kcache.shape):
+        raise RuntimeError("kcache / vcache shape mismatch")
+    if paged:
+        if page % 256 != 0:
+            raise RuntimeError("Paged KV cache block size must be divisible by 256")
+        if block_table_.shape[0] != B:
+            raise RuntimeError("block_table must have shape (batch_size, max_num_blocks_per_seq)")
+    elif cache_batch_idx_ is None and kcache.shape[0] != B:
+        raise RuntimeError("kcache batch size must match q (or pass cache_batch_idx)")
+    for nm, t in (("seqlens_k", seqlens_k_), ("cache_batch_idx", cache_batch_idx_)):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != (B,)):
+            raise RuntimeError(f"{nm} must be a contiguous int32 tensor of shape (batch_size)")
+    s_new = 0 if k_ is None else k_.shape[1]
+    if s_new > Sk:
+        raise RuntimeError("If key is supplied, it must have seqlen <= the seqlen of the KV cache")
+    if paged and seqlens_k_ is not None:  # the reference's guard (flash_api.cpp:1433-1447); costs a device->host sync
+        need = int(seqlens_k_.max().item()) + s_new
+        if need > Sk:
+            raise RuntimeError(f"Paged KV cache: max(seqlens_k){' + seqlen_knew' if s_new else ''} (= {need}) exceeds the capacity "
+                               f"addressable by block_table (max_num_blocks_per_seq * page_block_size = {Sk})")
+    out, f = _fp8_args(q, kcache, vcache, out_, (q_descale, k_descale, v_descale), B, Hk, (B, Sq, H, D))
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    if Sq == 1:  # one bottom-right aligned query row sees every key: no causal mask, no right bound
+        is_causal, window_size_right = False, -1
+    lib = _cabi.load()
+    with torch.cuda.device(q.device):
+        if k_ is not None:
+            if v_ is None or seqlens_k_ is None:
+                raise RuntimeError("If key is supplied, value and seqlens_k must also be passed in")
+            for t in (k_, v_):
+                if t.dtype != fp8 or tuple(t.shape) != (B, s_new, Hk, D) or t.stride(-1) != 1:
+                    raise RuntimeError("new key / value must be float8_e4m3fn of shape (batch_size, seqlen_new, num_heads_k, head_size) with a "
+                                       "contiguous last dimension")
+            ap = _cabi.FaKvAppendParams()
+            ap.knew, ap.vnew, ap.kcache, ap.vcache = _ptr(k_), _ptr(v_), _ptr(kcache), _ptr(vcache)
+            for nm, t in (("knew", k_), ("vnew", v_), ("kcache", kcache), ("vcache", vcache)):
+                setattr(ap, nm + "_batch_stride", t.stride(0)); setattr(ap, nm + "_row_stride", t.stride(1)); setattr(ap, nm + "_head_stride", t.stride(2))
+            ap.seqlens_k, ap.cache_batch_idx = _ptr(seqlens_k_), _ptr(cache_batch_idx_)
+            ap.block_table, ap.block_table_batch_stride = _ptr(block_table_), (block_table_.stride(0) if paged else 0)
+            ap.page_block_size = page
+            ap.b, ap.seqlen_new, ap.h_k, ap.d, ap.dtype = B, s_new, Hk, D, _cabi.FA_DTYPE_FP8_E4M3
+            if s_new > 0:
+                _cabi.check(lib.fa_kvcache_append(C.byref(ap), C.c_void_p(_stream_ptr(q.device))))
+        if Sk == 0:
+            out.zero_()
+            lse.fill_(float("inf"))
+        elif Sq > 0:
+            a = _cabi.FaFwdParams()
+            a.q, a.k, a.v, a.o, a.softmax_lse = _ptr(q), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(lse)
+            a.q_batch_stride, a.q_row_stride, a.q_head_stride = q.stride(0), q.stride(1), q.stride(2)
+            a.k_batch_stride, a.k_row_stride, a.k_head_stride = kcache.stride(0), kcache.stride(1), kcache.stride(2)
+            a.v_batch_stride, a.v_row_stride, a.v_head_stride = vcache.stride(0), vcache.stride(1), vcache.stride(2)
+            a.o_batch_stride, a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
+            a.seqused_k, a.seqused_k_add = _ptr(seqlens_k_), s_new
+            a.cache_batch_idx, a.block_table = _ptr(cache_batch_idx_), _ptr(block_table_)
+            a.block_table_batch_stride, a.page_block_size = (block_table_.stride(0) if paged else 0), page
+            a.b, a.h, a.h_k, a.d = B, H, Hk, D
+            a.seqlen_q, a.seqlen_k, a.total_q = Sq, Sk, B * Sq
+            a.dtype = _cabi.FA_DTYPE_FP8_E4M3
+            a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)
+            a.softmax_scale = float(softmax_scale)
+            a.num_splits = int(num_splits)
+            ws_bytes = lib.fa_fwd_workspace_bytes(C.byref(a))  # split-KV partials (0 when the keys are not split)
+            if ws_bytes > 0:
+                ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=q.device)
+                a.workspace, a.workspace_bytes = _ptr(ws), ws_bytes
+            _cabi.check(lib.fa_fwd_kvcache_fp8(C.byref(a), C.byref(f), C.c_void_p(_stream_ptr(q.device))))
     return [out, lse]

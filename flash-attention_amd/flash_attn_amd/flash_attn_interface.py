@@ -236,6 +236,30 @@ def _fp8_route(q, k, v, batch, dropout_p, softmax_scale, softcap, alibi_slopes, 
     return q.shape[-1] ** (-0.5) if softmax_scale is None else softmax_scale
 
 
+def _fp8_kvcache_route(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_leftpad, softcap, alibi_slopes, descales):
+    """FP8 KV cache (FA3's contract): q, the caches and the new k / v float8_e4m3fn, descales fp32 (B, Hk) or None.  Shapes and flags only: the
+    checks run before anything reaches the backend."""
+    fp8 = torch.float8_e4m3fn
+    if q.dtype != fp8 and k_cache.dtype != fp8 and v_cache.dtype != fp8:
+        raise RuntimeError("q_descale / k_descale / v_descale apply to float8_e4m3fn inputs only")
+    if not (q.dtype == k_cache.dtype == v_cache.dtype == fp8) or any(t is not None and t.dtype != fp8 for t in (k, v)):
+        raise RuntimeError("the fp8 KV cache takes float8_e4m3fn q, k_cache, v_cache and new k / v: mixed dtypes (bf16 q against an fp8 cache) "
+                           "are not supported")
+    if rotary_cos is not None or rotary_sin is not None:
+        raise RuntimeError("the fp8 KV cache does not support rotary cos / sin: rotating quantised values needs a requantisation; rotate "
+                           "before quantising")
+    if cache_leftpad is not None:
+        raise RuntimeError("the fp8 KV cache does not support cache_leftpad")
+    if softcap != 0.0:
+        raise RuntimeError("the fp8 KV cache does not support softcap")
+    if alibi_slopes is not None:
+        raise RuntimeError("the fp8 KV cache does not support ALiBi (alibi_slopes)")
+    batch, hk = q.shape[0], k_cache.shape[-2]
+    for name, t in zip(("q_descale", "k_descale", "v_descale"), descales):
+        if t is not None and tuple(t.shape) != (batch, hk):
+            raise RuntimeError(f"{name} must have shape (batch_size, num_heads_k) = ({batch}, {hk}), got {tuple(t.shape)}")
+
+
 # An exported program (torch.export) holds the raw ops, not the autograd.Function wrappers below; with an autograd formula on
 # the two forward ops such a graph can still be differentiated (the reference registers one for its FA3 ops, the precedent
 # hopper/test_torch_compile_and_export.py exercises; its FA2 ops have none).  Inside the Function wrappers the ops run
@@ -537,18 +561,31 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False):
+                            return_softmax_lse=False, *, q_descale=None, k_descale=None, v_descale=None):
     """Inference attention against a KV cache (reference :1485-1627).  If k / v are given they are written into the
     cache in place at rows ``cache_seqlens[b] ..`` before attending; ``cache_seqlens`` may be an int or an int32
     tensor (batch,); ``cache_batch_idx`` selects cache rows; ``block_table`` selects pages of a paged cache
     (num_blocks, page, Hk, D); ``rotary_cos/sin`` (seqlen_ro, rotary_dim/2) rotate the new keys at positions
     cache_seqlens + i and the queries likewise (all at cache_seqlens unless causal / local); ``cache_leftpad`` gives the
-    first valid cache row of each entry.  No backward."""
+    first valid cache row of each entry.  No backward.
+    float8_e4m3fn q / caches / new k, v (FA3's fp8 KV cache): optional fp32 (B, Hk) ``q_descale`` / ``k_descale`` / ``v_descale`` indexed by the
+    batch entry of q, bf16 out, head dims 64 / 128; new keys / values are appended as bytes (quantise them with the cache's scale); rotary,
+    ``cache_leftpad``, ALiBi and softcap are refused."""
     q, k, v = (_unit_stride_last(t) for t in (q, k, v))
+    fp8 = (q.dtype == torch.float8_e4m3fn or k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn
+           or q_descale is not None or k_descale is not None or v_descale is not None)
+    if fp8:
+        _fp8_kvcache_route(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_leftpad, softcap, alibi_slopes, (q_descale, k_descale, v_descale))
     if softmax_scale is None:
         softmax_scale = q.shape[-1] ** (-0.5)
     if cache_seqlens is not None and isinstance(cache_seqlens, int):
         cache_seqlens = torch.full((q.shape[0],), cache_seqlens, dtype=torch.int32, device=k_cache.device)
+    if fp8:
+        out, lse = flash_attn_gpu.fwd_kvcache_fp8(
+            q, k_cache, v_cache, k, v, cache_seqlens, None if cache_batch_idx is None else cache_batch_idx.contiguous(),
+            None if block_table is None else _unit_stride_last(block_table), None, q_descale, k_descale, v_descale, softmax_scale, causal,
+            window_size[0], window_size[1], num_splits)
+        return (out, lse) if return_softmax_lse else out
     out, lse = flash_attn_gpu.fwd_kvcache(
         q, k_cache, v_cache, k, v, cache_seqlens, _unit_stride_last(rotary_cos), _unit_stride_last(rotary_sin),
         None if cache_batch_idx is None else cache_batch_idx.contiguous(), cache_leftpad,

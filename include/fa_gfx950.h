@@ -45,7 +45,7 @@ extern "C" {
 
 #define FA_ABI_VERSION 6
 
-enum { FA_DTYPE_FP16 = 0, FA_DTYPE_BF16 = 1, FA_DTYPE_FP8_E4M3 = 2 /* OCP e4m3 (float8_e4m3fn): fa_fwd_fp8 / fa_varlen_fwd_fp8 only */ };
+enum { FA_DTYPE_FP16 = 0, FA_DTYPE_BF16 = 1, FA_DTYPE_FP8_E4M3 = 2 /* OCP e4m3 (float8_e4m3fn): fa_fwd_fp8 / fa_varlen_fwd_fp8 / fa_fwd_kvcache_fp8 and fa_kvcache_append only */ };
 
 enum {
   FA_OK = 0,
@@ -198,7 +198,7 @@ typedef struct FaBwdParams {
                                    past it are not written */
 } FaBwdParams;
 
-/* Descale factors of the FP8 forward (fa_fwd_fp8 / fa_varlen_fwd_fp8): fp32 device tensors of shape (B, Hk) -- per KV head, FA3's
+/* Descale factors of the FP8 forwards (fa_fwd_fp8 / fa_varlen_fwd_fp8 / fa_fwd_kvcache_fp8): fp32 device tensors of shape (B, Hk) -- per KV head, FA3's
  * q_descale / k_descale / v_descale (hopper/flash_api.cpp) -- with any strides (in elements).  A NULL pointer means 1.0. */
 typedef struct FaFp8Params {
   const float* q_descale;
@@ -226,7 +226,7 @@ void fa_knobs_reload(void);
 /* Which kernels the calling thread's last fa_fwd* / fa_bwd* call enqueued (for tests and the benchmark's labels; the
  * reference exposes nothing comparable -- its dispatch is compile-time, flash_fwd_launch_template.h).  Fills up to n of
  * FA_SCHEDULE_FIELDS int32: {forward kernel id (0 none, 1 lock-step fa_fwd_kernel, 2 pipelined fa_fwd_il_kernel,
- * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
+ * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel, 5 FP8 KV-cache fa_fwd_fp8_kv_kernel), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
  * varlen work list used, head dim, bf16, dQ-kernel waves, backward work lists used, backward spilled dS (5 contractions),
  * query heads packed into the rows of a block (fa_fwd_kvcache, 1 = none), dK/dV schedule (8 waves x 32 keys, 4 at head dim 256,
  * or 64 = 4 waves x 64 keys)}; returns FA_SCHEDULE_FIELDS (fields are only ever appended). */
@@ -257,10 +257,19 @@ int fa_varlen_fwd(const FaFwdParams* params, void* stream);
  * aligned), o is bf16 (strides multiples of 8 elements).  S = softmax_scale * q_descale * k_descale * q.k^T on the exact fp8 values, P = softmax(S)
  * rounded to e4m3, o = P.(v_descale * v); softmax_lse as fa_fwd.  fp8 may be NULL (all descales 1).  Causal / window masks, MHA / GQA / MQA,
  * head dims 64 and 128.  FA_ERR_UNSUPPORTED (with a message naming it) for any other head dim, softcap, ALiBi, dropout, return_softmax,
- * seqused_q / seqused_k, leftpad_k, block_table and the KV-cache arguments; there is no fp8 KV-cache entry point and no fp8 backward.
+ * seqused_q / seqused_k, leftpad_k, block_table and the KV-cache arguments (those belong to fa_fwd_kvcache_fp8); there is no fp8 backward.
  * fa_varlen_fwd_fp8: packed batch as fa_varlen_fwd (the workspace of fa_fwd_workspace_bytes holds the work list of an uneven batch). */
 int fa_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
 int fa_varlen_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
+/* Inference forward of e4m3 queries against an e4m3 KV cache (FA3's flash_attn_with_kvcache with q_descale / k_descale / v_descale): the contract of
+ * fa_fwd_fp8 -- layout rules, math, bf16 o, fp32 softmax_lse, descales (B, Hk) indexed by the batch entry of q, not by the cache row -- with the cache
+ * arguments of fa_fwd_kvcache: seqused_k (+ seqused_k_add), cache_batch_idx, block_table (pages of a multiple of 256 keys; seqlen_k = max_blocks * page),
+ * num_splits and the workspace of fa_fwd_workspace_bytes; masks are aligned to each entry's own length; the query heads of a KV group are packed into
+ * the rows of a block when group * seqlen_q <= 128.  Head dims 64 and 128.  FA_ERR_UNSUPPORTED (with a message naming it) for softcap, ALiBi,
+ * leftpad_k, dropout / return_softmax, seqused_q and any other head dim.  New keys are appended first with fa_kvcache_append (dtype FA_DTYPE_FP8_E4M3:
+ * a byte copy, d a multiple of 16, strides multiples of 16 bytes, pointers 16-byte aligned) -- the caller quantises them with the cache's scale;
+ * fa_rotary refuses e4m3 (rotating quantised values needs a requantisation nobody has defined). */
+int fa_fwd_kvcache_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
 /* Inference forward against a KV cache: fa_fwd plus seqused_k (cache_seqlens), cache_batch_idx and/or a
  * paged cache (block_table).  k/v point at the cache.  No backward. */
 int fa_fwd_kvcache(const FaFwdParams* params, void* stream);
@@ -268,7 +277,7 @@ int fa_fwd_kvcache(const FaFwdParams* params, void* stream);
 int fa_kvcache_append(const FaKvAppendParams* params, void* stream);
 /* Writes {seed, offset} to a device rng_state (2 x u64) in stream order (binder helper for p_dropout > 0). */
 int fa_set_rng_state(uint64_t seed, uint64_t offset, uint64_t* rng_state, void* stream);
-/* Bytes of split-KV scratch fa_fwd_kvcache needs for this problem with params->num_splits (0 is possible). */
+/* Bytes of split-KV scratch fa_fwd_kvcache / fa_fwd_kvcache_fp8 need for this problem with params->num_splits (0 is possible). */
 int64_t fa_fwd_workspace_bytes(const FaFwdParams* params);
 /* Rotary embedding of q / new keys ahead of fa_kvcache_append + fa_fwd_kvcache (y may alias x). */
 int fa_rotary(const FaRotaryParams* params, void* stream);
