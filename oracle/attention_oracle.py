@@ -137,8 +137,12 @@ def _scores(qh, kh, scale, softcap, vis, alibi_slope, shift):
 
 def attention_fwd(q, k, v, softmax_scale: Optional[float] = None, causal: bool = False,
                   window: Tuple[int, int] = (-1, -1), softcap: float = 0.0,
-                  alibi_slopes=None, dropout_p: float = 0.0, dropout_mask=None):
+                  alibi_slopes=None, dropout_p: float = 0.0, dropout_mask=None, max_seqlen_k: Optional[int] = None):
     """Forward oracle.
+
+    ``max_seqlen_k``: the key length the host API normalises the window by when it is not this call's own --
+    one sequence of a packed batch (flash_api.cpp mha_varlen_fwd: the batch's ``max_seqlen_k``); a bound
+    that survives applies to the sequence literally, also where it exceeds that sequence's length.
 
     Dropout (tests/test_util.py:262-269, flash_fwd_kernel.h:357-368): the normalised probabilities are
     multiplied by ``dropout_mask`` (B,H,Sq,Sk, True = keep) and by 1/(1-dropout_p) before the product
@@ -153,7 +157,7 @@ def attention_fwd(q, k, v, softmax_scale: Optional[float] = None, causal: bool =
     Sk, Hk = k.shape[1], k.shape[2]
     assert H % Hk == 0
     scale = D ** -0.5 if softmax_scale is None else float(softmax_scale)
-    _, wl, wr = normalize_window(Sq, Sk, causal, window[0], window[1], alibi_slopes is not None)
+    _, wl, wr = normalize_window(Sq, Sk if max_seqlen_k is None else max_seqlen_k, causal, window[0], window[1], alibi_slopes is not None)
     vis = visible_mask(Sq, Sk, wl, wr)
     out = np.zeros((B, Sq, H, D))
     lse = np.full((B, H, Sq), np.inf)
@@ -184,8 +188,8 @@ def attention_fwd(q, k, v, softmax_scale: Optional[float] = None, causal: bool =
 
 def attention_bwd(dout, q, k, v, out=None, lse=None, softmax_scale: Optional[float] = None,
                   causal: bool = False, window: Tuple[int, int] = (-1, -1), softcap: float = 0.0,
-                  alibi_slopes=None, dropout_p: float = 0.0, dropout_mask=None):
-    """Backward oracle: returns dq (B,Sq,H,D), dk, dv (B,Sk,Hk,D), delta (B,H,Sq), all f64.
+                  alibi_slopes=None, dropout_p: float = 0.0, dropout_mask=None, max_seqlen_k: Optional[int] = None):
+    """Backward oracle (``max_seqlen_k``: see attention_fwd): returns dq (B,Sq,H,D), dk, dv (B,Sk,Hk,D), delta (B,H,Sq), all f64.
 
     With dropout (flash_bwd_kernel.h:560-600): Z = mask/(1-p); dV = (P*Z)^T dO, dP = (dO V^T)*Z,
     delta = rowsum(dO*O) with the dropped O.
@@ -201,9 +205,9 @@ def attention_bwd(dout, q, k, v, out=None, lse=None, softmax_scale: Optional[flo
     Sk, Hk = k.shape[1], k.shape[2]
     scale = D ** -0.5 if softmax_scale is None else float(softmax_scale)
     if out is None or lse is None:
-        out, lse = attention_fwd(q, k, v, scale, causal, window, softcap, alibi_slopes, dropout_p, dropout_mask)
+        out, lse = attention_fwd(q, k, v, scale, causal, window, softcap, alibi_slopes, dropout_p, dropout_mask, max_seqlen_k)
     out, lse = _f64(out), _f64(lse)
-    _, wl, wr = normalize_window(Sq, Sk, causal, window[0], window[1], alibi_slopes is not None)
+    _, wl, wr = normalize_window(Sq, Sk if max_seqlen_k is None else max_seqlen_k, causal, window[0], window[1], alibi_slopes is not None)
     vis = visible_mask(Sq, Sk, wl, wr)
     dq = np.zeros_like(q)
     dk = np.zeros_like(k)
@@ -249,7 +253,7 @@ def varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale: Optional[floa
     """Packed varlen forward: q (total_q,H,D), k,v (total_k,Hk,D), cu_seqlens int32 (B+1).
 
     Sequence b owns rows cu[b] .. cu[b+1]-1 (block_info.h:12-45); result equals the
-    concatenation of per-sequence fixed-length calls.  Returns out (total_q,H,D), lse (H,total_q).
+    concatenation of per-sequence fixed-length calls whose window is normalised by the longest key sequence.  Returns out (total_q,H,D), lse (H,total_q).
     """
     q, k, v = _f64(q), _f64(k), _f64(v)
     cq, ck = _as_int_list(cu_seqlens_q), _as_int_list(cu_seqlens_k)
@@ -259,6 +263,7 @@ def varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale: Optional[floa
     out = np.zeros_like(q)
     lse = np.full((H, q.shape[0]), np.inf)
     slopes = None if alibi_slopes is None else _f64(alibi_slopes)
+    max_k = max(b1 - b0 for b0, b1 in zip(ck[:-1], ck[1:]))   # the window is normalised once, by the batch's longest key sequence
     for b in range(len(cq) - 1):
         q0, q1, k0, k1 = cq[b], cq[b + 1], ck[b], ck[b + 1]
         if q1 == q0:
@@ -266,7 +271,7 @@ def varlen_fwd(q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale: Optional[floa
         sl = None
         if slopes is not None:
             sl = slopes if slopes.ndim == 1 else slopes[b:b + 1]
-        o, l = attention_fwd(q[None, q0:q1], k[None, k0:k1], v[None, k0:k1], scale, causal, window, softcap, sl)
+        o, l = attention_fwd(q[None, q0:q1], k[None, k0:k1], v[None, k0:k1], scale, causal, window, softcap, sl, max_seqlen_k=max_k)
         out[q0:q1] = o[0]
         lse[:, q0:q1] = l[0]
     return out, lse
@@ -287,6 +292,7 @@ def varlen_bwd(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale: Optiona
     slopes = None if alibi_slopes is None else _f64(alibi_slopes)
     out64 = None if out is None else _f64(out)
     lse64 = None if lse is None else _f64(lse)
+    max_k = max(b1 - b0 for b0, b1 in zip(ck[:-1], ck[1:]))
     for b in range(len(cq) - 1):
         q0, q1, k0, k1 = cq[b], cq[b + 1], ck[b], ck[b + 1]
         if q1 == q0:
@@ -297,7 +303,7 @@ def varlen_bwd(dout, q, k, v, cu_seqlens_q, cu_seqlens_k, softmax_scale: Optiona
         o = None if out64 is None else out64[None, q0:q1]
         l = None if lse64 is None else lse64[None, :, q0:q1]
         a, bb, c, d = attention_bwd(dout[None, q0:q1], q[None, q0:q1], k[None, k0:k1], v[None, k0:k1],
-                                    o, l, scale, causal, window, softcap, sl)
+                                    o, l, scale, causal, window, softcap, sl, max_seqlen_k=max_k)
         dq[q0:q1] = a[0]
         dk[k0:k1] += bb[0]
         dv[k0:k1] += c[0]

@@ -81,3 +81,78 @@ def attention_torch(q, k, v, causal=False, window=(-1, -1), softmax_scale=None, 
 
 def max_abs(a, b):
     return float((a.double() - b.double()).abs().max()) if a.numel() else 0.0
+
+
+MATRIX_FAMILIES = ("fixed", "varlen", "long")
+
+
+def matrix_files(family):
+    import glob
+    import os
+    return sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_matrix_%s_*.npz" % family)))
+
+
+def matrix_names(family):
+    """Case names of one family of tests/golden/ref_matrix_<family>_NN.npz (tests/golden/make_golden.py MATRIX), without reading the arrays."""
+    names = []
+    for path in matrix_files(family):
+        with np.load(path) as z:
+            for k in z.files:
+                if "/" in k and k.split("/")[0] not in names:
+                    names.append(k.split("/")[0])
+    return names
+
+
+def matrix_head_dims(family):
+    """{case name: head dim}, from the meta arrays alone."""
+    dims = {}
+    for path in matrix_files(family):
+        with np.load(path) as z:
+            dims.update({k.split("/")[0]: int(z[k][5]) for k in z.files if k.endswith("/meta")})
+    return dims
+
+
+_MATRIX_CACHE = {}
+
+
+def load_matrix(family):
+    """{case name: {key: array}} of one family; arrays the generator cut into <key>__partN pieces are joined again."""
+    if family in _MATRIX_CACHE:
+        return _MATRIX_CACHE[family]
+    flat = {}
+    for path in matrix_files(family):
+        with np.load(path) as z:
+            flat.update({k: z[k] for k in z.files})
+    for k in [k for k in flat if k.endswith("__shape")]:
+        base = k[: -len("__shape")]
+        n = sum(1 for x in flat if x.startswith(base + "__part"))
+        flat[base] = np.concatenate([flat.pop("%s__part%d" % (base, i)) for i in range(n)]).reshape(tuple(flat.pop(k)))
+    cases = {}
+    for k, a in flat.items():
+        if "/" in k:
+            cases.setdefault(k.split("/")[0], {})[k.split("/", 1)[1]] = a
+    cases["README"] = str(flat["README"])
+    _MATRIX_CACHE[family] = cases
+    return cases
+
+
+def matrix_meta(case):
+    m = case_meta(case)
+    m["ratio"] = m["H"] // m["Hk"]
+    m["rows"] = case.get("rows")
+    m["bwd_from_oracle"] = "bwd_from_oracle" in case
+    m["packed"] = "qmask" in case
+    return m
+
+
+def matrix_bound(case, tensor, dtype_name, ref_absmax=None, err_pt=None):
+    """The reference's rule with the reference's recorded baseline (tests/test_flash_attn.py:1130-1132): |out - ref| <= 2 err_pt[out] + 1e-5, gradients
+    <= 3 err_pt[g] + 1e-4, err_pt = the fixture's err_pt_<dtype> (attention_ref in that dtype on the CPU) unless the caller brings its own.  Softcap cases have no
+    differentiable reference in the input dtype (in-place tanh): their gradients take the bound of test_bwd_gpu.py test_softcap_backward_vs_oracle."""
+    i = ("out", "dq", "dk", "dv").index(tensor)
+    e = float(case["err_pt_" + dtype_name][i]) if err_pt is None else err_pt
+    if i == 0:
+        return 2 * e + 1e-5
+    if "bwd_from_oracle" in case:
+        return 3e-2 * max(1.0, ref_absmax)
+    return 3 * e + 1e-4

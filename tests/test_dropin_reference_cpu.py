@@ -43,7 +43,7 @@ print("DROPIN_OK")
 
 def _reference_root():
     # Opt-in only: these tests import and EXECUTE a third-party package.  Nothing is auto-discovered; the caller names the tree
-    # (FLASH_ATTN_REF=/root/reference in the build container, FLASH_ATTN_REF=<repo>/_ref_tmp for tools/ref_suite/run.sh on a GPU box).
+    # (FLASH_ATTN_REF=<a checkout of the reference>, on a machine that has one).
     cand = os.environ.get("FLASH_ATTN_REF")
     if cand and os.path.exists(os.path.join(cand, "flash_attn", "flash_attn_interface.py")):
         return cand

@@ -1,8 +1,8 @@
 """The literal drop-in: the REFERENCE's Python package (flash_attn/flash_attn_interface.py, its torch.library custom ops
 flash_attn::_flash_attn_forward / _backward / ..., :84-458) importing OUR module `flash_attn_2_cuda`, forward + backward
 against the fp64 oracle.  The reference tree is not part of this repository and does not exist on the driver's GPU box:
-the test runs only when $FLASH_ATTN_REF names a readable tree (opt-in: it executes third-party code; tools/ref_suite/run.sh points it at
-the git-ignored scratch copy <repo>/_ref_tmp; recorded runs: profiles/r02_dropin_reference.txt, profiles/r04_reference_suite.txt) and SKIPS -- saying so -- otherwise."""
+the test runs only when $FLASH_ATTN_REF names a readable tree (opt-in: it executes third-party code; recorded runs: profiles/r02_dropin_reference.txt,
+profiles/r04_reference_suite.txt) and SKIPS -- saying so -- otherwise.  No copy of that tree is made or shipped anywhere by this repository's tools."""
 import importlib
 import os
 import sys
@@ -19,7 +19,7 @@ PKG = os.path.join(ROOT, "flash-attention_amd")
 
 def _reference_root():
     # Opt-in only: these tests import and EXECUTE a third-party package.  Nothing is auto-discovered; the caller names the tree
-    # (FLASH_ATTN_REF=/root/reference in the build container, FLASH_ATTN_REF=<repo>/_ref_tmp for tools/ref_suite/run.sh on a GPU box).
+    # (FLASH_ATTN_REF=<a checkout of the reference>, on a machine that has one).
     cand = os.environ.get("FLASH_ATTN_REF")
     if cand and os.path.exists(os.path.join(cand, "flash_attn", "flash_attn_interface.py")):
         return cand

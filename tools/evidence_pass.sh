@@ -1,7 +1,7 @@
 #!/bin/bash
 # End-of-round evidence pass on one GPU box (usage: gpurun -- 'bash tools/evidence_pass.sh <tag>'): the GPU suite, the bench line (PMC traffic + CPU baseline), kernel stats of
 # the same bench command under rocprofv3, in-kernel clock stamps of the forward (if gpurun_abl/libfa_abl_2048.so was built here first), SQ counters of the forward and the
-# backward at config 3, and -- when the git-ignored scratch copy _ref_tmp/ travelled along (tools/ref_suite/make_scratch.sh) -- the reference's own suites.
+# backward at config 3.
 # Output: gpurun_out/<tag>/ ; copy what is to be judged into profiles/.
 # (the suite runs serially, as the driver runs it: 4.5 min; under `-n 6` the six processes share one GPU and eight host cores and take 11 min)
 TAG=${1:-final}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
@@ -15,6 +15,5 @@ head -30 $O/bench_kernel_stats.txt
 [ -f $R/gpurun_abl/libfa_abl_2048.so ] && FA_GFX950_LIB=$R/gpurun_abl/libfa_abl_2048.so python tools/w64_stamps.py > $O/w64_stamps.txt 2>&1
 bash tools/pmc_fwd.sh ${TAG}_c3 4 4096 32 128 1 > $O/fwd_w64_sq_counters_causal.txt 2>&1
 bash tools/pmc_bwd.sh $TAG > /dev/null 2>&1; cp gpurun_out/pmc_bwd_$TAG.txt $O/bwd_sq_counters.txt
-[ -d $R/_ref_tmp ] && REF_SUITE_SHARD_TIMEOUT=${REF_SUITE_SHARD_TIMEOUT:-600} bash tools/ref_suite/run.sh ${REF_SUITE_PER_FN:-250} > $O/ref_suite_stdout.txt 2>&1 && cp gpurun_out/ref_suite/summary.txt $O/ref_suite_summary.txt
-cut -c1-500 $O/bench_line.json; tail -3 $O/bench_time.txt; tail -12 $O/ref_suite_summary.txt 2>/dev/null | cut -c1-200
+cut -c1-500 $O/bench_line.json; tail -3 $O/bench_time.txt
 rm -rf $O/kt $R/gpurun_out/pmc_${TAG}_c3/p? $R/gpurun_out/pmcb_$TAG

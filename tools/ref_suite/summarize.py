@@ -1,10 +1,11 @@
-"""Per-test-function pass / fail / skip table of a tools/ref_suite/run.sh run (gpurun_out/ref_suite/*.jsonl)."""
+"""Per-test-function pass / fail / skip table of the *.jsonl files that tools/ref_suite/conftest.py wrote (the runs behind profiles/r0[456]_reference_suite*.txt; the
+scripts that made those runs are deleted: the reference's Python does not travel to a GPU machine any more)."""
 import glob
 import json
 import os
 import sys
 
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/ref_suite"
+d = sys.argv[1]
 tot = {"passed": 0, "failed": 0, "skipped": 0}
 fails = []
 print(f"{'suite':6s} {'test function':44s} {'parametrised':>12s} {'sampled':>8s} {'passed':>7s} {'failed':>7s} {'skipped':>8s}")
