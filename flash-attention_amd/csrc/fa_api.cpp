@@ -131,7 +131,7 @@ template <typename K> void fill_dropout(K& k, float p_dropout, const uint64_t* r
 // of once per query head.  Returns g (1 = no packing).
 int pack_group(const FaFwdParams* a) {
   const int g = a->h_k > 0 ? a->h / a->h_k : 1;
-  if (g <= 1 || !fa::knobs().pack_gqa || a->cu_seqlens_q || a->seqused_q || a->p_dropout > 0.f || a->seqlen_q < 1 || (long)a->seqlen_q * g > 128) return 1;
+  if (g <= 1 || !fa::knobs().pack_gqa || (a->d_v > 0 && a->d_v != a->d) || a->cu_seqlens_q || a->seqused_q || a->p_dropout > 0.f || a->seqlen_q < 1 || (long)a->seqlen_q * g > 128) return 1;
   return g;
 }
 int choose_splits(const FaFwdParams* a, int& split_tiles) {
@@ -222,11 +222,31 @@ int fwd_block_rows(const FaFwdParams* a, int nw, bool split) {
   return nw == 16 ? 256 : 32 * nw;
 }
 // varlen work list: worth a pre-pass when a max_seqlen-sized grid would be mostly empty slots
-int64_t varlen_list_entries(const FaFwdParams* a, int bm) {
+// (min_dense: the smallest dense grid, in blocks per head, for which the pre-pass is launched.  64 is the measured choice of the kernels that launch the dense grid
+// whatever the list says.  The kernel for a v head dim of its own sizes its grid from the list (work_bound * h workgroups, as fa_fwd_il does), so the list saves it
+// launches at any size; its 32 is a choice, not a measurement)
+int64_t varlen_list_entries(const FaFwdParams* a, int bm, int min_dense = 64) {
   if (fa::knobs().varlen_list == 0) return 0;  // debugging switch: always the dense grid
   const int64_t dense = (int64_t)a->b * ((a->seqlen_q + bm - 1) / bm);
   const int64_t bound = (int64_t)a->total_q / bm + a->b;
-  return (dense * 4 > bound * 5 && dense >= 64) ? bound : 0;
+  return (dense * 4 > bound * 5 && dense >= min_dense) ? bound : 0;
+}
+constexpr int kDvListMinDense = 32;
+
+// Launches the schedule pre-pass of a packed forward with `bm`-row blocks into the caller's workspace and points k at the list; without a list (a dense enough
+// batch, or no workspace) k is left alone.
+int fwd_work_list(const FaFwdParams* a, int bm, int min_dense, int wl, int wr, void* stream, fa::FwdK& k) {
+  const int64_t entries = varlen_list_entries(a, bm, min_dense);
+  if (entries <= 0 || !a->workspace || a->workspace_bytes < (entries + 1) * 8) return FA_OK;
+  fa::SchedK sk{};
+  sk.cu_a = a->cu_seqlens_q; sk.cu_o = a->cu_seqlens_k; sk.seqused_o = a->seqused_k;
+  sk.list = (int2*)a->workspace; sk.nb = a->b; sk.blk = bm; sk.bound = (int)entries; sk.wl = wl; sk.wr = wr; sk.keys_blocked = 0;
+  sk.work_shift = fa::sched_work_shift(a->seqlen_k);
+  if (fa::launch_varlen_schedule(sk, (hipStream_t)stream) != 0)
+    return fail(FA_ERR_LAUNCH, "schedule kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+  k.work_list = (const int2*)a->workspace;
+  k.work_bound = (int)entries;
+  return FA_OK;
 }
 
 int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool forward = false) {
@@ -240,6 +260,28 @@ int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool fo
   if (softcap < 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "softcap must be non-negative");
   return FA_OK;
 }
+
+// A v / o head dim of its own (FaFwdParams::d_v / FaBwdParams::d_v; 0 = d).  One pair is built: q / k 192, v / o 128 (fa_fwd_dv.hip; the backward runs the
+// 256-pitch kernels of head dim 192 with a value width of 128, fa_bwd.hip).  Everything else about such a call is refused here, before anything touches the
+// device, with a message that names both head dims or the argument.
+inline int value_dim(int d, int d_v) { return d_v > 0 ? d_v : d; }
+int check_value_dim(const char* fn, int d, int d_v, float p_dropout, float softcap, const void* alibi, const void* randval, const void* block_table,
+                    const void* leftpad_k, bool kvcache, bool fp8) {
+  if (d_v < 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: d_v must be non-negative (0 = the head dim of q / k), got %d", fn, d_v);
+  if (d_v == 0 || d_v == d) return FA_OK;
+  if (fp8) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the fp8 path has no kernel for a v head dim that differs from q / k", fn, d, d_v);
+  if (kvcache) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the KV-cache path has no kernel for a v head dim that differs from q / k", fn, d, d_v);
+  if (d != 192 || d_v != 128)
+    return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the only built pair with a v head dim that differs from q / k is (192, 128)", fn, d, d_v);
+  if (p_dropout > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support dropout (p_dropout)", fn, d, d_v);
+  if (softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support softcap", fn, d, d_v);
+  if (alibi) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support ALiBi (alibi_slopes)", fn, d, d_v);
+  if (randval) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support return_softmax", fn, d, d_v);
+  if (block_table) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support block_table (paged KV)", fn, d, d_v);
+  if (leftpad_k) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support leftpad_k", fn, d, d_v);
+  return FA_OK;
+}
+inline bool own_value_dim(int d, int d_v) { return d_v > 0 && d_v != d; }
 
 // What the heuristic's pick becomes once the features have had their say (shared by do_fwd and fa_fwd_schedule_query):
 //   64 = the 64-rows-per-wave kernel: plain attention, ALiBi under a right bound on the diagonal (its FEAT_ALIBI variant: the bias rides in the
@@ -268,6 +310,9 @@ int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true)) return rc;
+  if (int rc = check_value_dim(kvcache ? "fa_fwd_kvcache" : varlen ? "fa_varlen_fwd" : "fa_fwd", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, a->randval,
+                               a->block_table, a->leftpad_k, kvcache || a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;
+  const bool own_dv = own_value_dim(a->d, a->d_v);
   if (!a->q || !a->k || !a->v || !a->o || !a->softmax_lse)
     return fail(FA_ERR_INVALID_ARGUMENT, "q, k, v, o and softmax_lse must be non-NULL");
   if (varlen != (a->cu_seqlens_q != nullptr) || varlen != (a->cu_seqlens_k != nullptr))
@@ -333,6 +378,19 @@ int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false
   const bool bounded = dk != a->d;
   if (bounded) k.d_chunks = a->d / 8;
   if (dk > 128 || head_dim_trimmed(dk) || bounded) nw = 4;  // head dim 256: one 4-wave lock-step workgroup per CU (512-register budget); trimmed / bounded dims: 4-wave lock-step
+  if (own_dv) {  // q / k 192, v / o 128: fa_fwd_dv_kernel, 4 waves x 32 rows (no key splits, no packing: refused above / pack_group)
+    constexpr int bm = 128;
+    k.nmb = (k.sq + bm - 1) / bm;
+    if (varlen) {
+      if (int rc = fwd_work_list(a, bm, kDvListMinDense, wl, wr, stream, k)) return rc;
+    }
+    fa::choose_units(a->b, a->h_k, k.hk_ratio, k.nmb, k.n_units, k.unit_size, k.unit_hpx);
+    const int rc = fa::launch_fwd_dv(k, a->dtype == FA_DTYPE_BF16, a->d, a->d_v, (hipStream_t)stream);
+    if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no forward kernel for head dims (%d, %d)", a->d, a->d_v);
+    if (rc != 0) return fail(FA_ERR_LAUNCH, "forward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    fa::last_schedule().fwd_pack = 1;
+    return FA_OK;
+  }
   // decode: split the keys over several workgroups when (batch x heads) cannot fill the chip
   if (kvcache) {
     int split_tiles = 0;
@@ -354,23 +412,13 @@ int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false
   const int bm = w64 ? 256 : il ? 32 * (nw - 30) : fa::fwd_block_m(nw);
   k.nmb = (k.sq + bm - 1) / bm;
   if (varlen && !kvcache) {  // uneven packed batch: enumerate the non-empty query blocks, heaviest first
-    const int64_t entries = varlen_list_entries(a, bm);
-    if (entries > 0 && a->workspace && a->workspace_bytes >= (entries + 1) * 8) {
-      fa::SchedK sk{};
-      sk.cu_a = a->cu_seqlens_q; sk.cu_o = a->cu_seqlens_k; sk.seqused_o = a->seqused_k;
-      sk.list = (int2*)a->workspace; sk.nb = a->b; sk.blk = bm; sk.bound = (int)entries; sk.wl = wl; sk.wr = wr; sk.keys_blocked = 0;
-      sk.work_shift = fa::sched_work_shift(a->seqlen_k);
-      if (fa::launch_varlen_schedule(sk, (hipStream_t)stream) != 0)
-        return fail(FA_ERR_LAUNCH, "schedule kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-      k.work_list = (const int2*)a->workspace;
-      k.work_bound = (int)entries;
-    }
+    if (int rc = fwd_work_list(a, bm, 64, wl, wr, stream, k)) return rc;
   }
   fa::choose_units(a->b, a->h_k, k.hk_ratio, k.nmb * k.n_splits, k.n_units, k.unit_size, k.unit_hpx);
   int rc = w64  ? fa::launch_fwd_w64(k, a->dtype == FA_DTYPE_BF16, dk, (hipStream_t)stream)
            : il ? fa::launch_fwd_il(k, a->dtype == FA_DTYPE_BF16, dk, nw - 30, (hipStream_t)stream)
                 : fa::launch_fwd(k, a->dtype == FA_DTYPE_BF16, dk, nw, (hipStream_t)stream);
-  if (rc == 0) fa::last_schedule().fwd_pack = k.pack_g;
+  if (rc == 0) { fa::last_schedule().fwd_pack = k.pack_g; fa::last_schedule().dv = fa::last_schedule().d; }
   if (rc == 0 && k.n_splits > 1) rc = fa::launch_splitkv_combine(k, a->dtype == FA_DTYPE_BF16, dk, (hipStream_t)stream);
   if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no forward kernel for head dim %d", a->d);
   if (rc == -3)
@@ -452,6 +500,7 @@ int fill_bwd(const FaBwdParams* a, bool varlen, fa::BwdK& k) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap)) return rc;
+  if (int rc = check_value_dim(varlen ? "fa_varlen_bwd" : "fa_bwd", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, nullptr, nullptr, nullptr, false, false)) return rc;
   if (!a->dout || !a->q || !a->k || !a->v || !a->o || !a->softmax_lse || !a->dq || !a->dk || !a->dv || !a->softmax_d)
     return fail(FA_ERR_INVALID_ARGUMENT, "dout, q, k, v, o, softmax_lse, dq, dk, dv and softmax_d must be non-NULL");
   if (varlen != (a->cu_seqlens_q != nullptr) || varlen != (a->cu_seqlens_k != nullptr))
@@ -613,9 +662,9 @@ bool bwd_c5_plan(const FaBwdParams* a, C5Plan& pl) {
 // heads each, BwdK::kv_in_shift tells the kernels which real K / V head to read --, their partial dK / dV go to a workspace [b][sk][h_k * gs][d] in the input dtype and
 // one small kernel sums them (the reference's own form: per-query-head dK / dV summed by at::sum_out, flash_api.cpp:1000-1004).  Fixed-length batches, head dims the
 // kernels hold natively; gs = the smallest power of two (<= 8) that brings the grid to 1024 workgroups, or the whole group.
-struct GsplitPlan { int gs, shift; int64_t bytes; };
+struct GsplitPlan { int gs, shift; int64_t bytes, dk_bytes; };
 bool bwd_gsplit_plan(const FaBwdParams* a, GsplitPlan& pl) {
-  pl = GsplitPlan{1, 0, 0};
+  pl = GsplitPlan{1, 0, 0, 0};
   if (fa::knobs().bwd_gsplit == 0 || a->cu_seqlens_q || a->cu_seqlens_k || a->seqused_q || a->seqused_k || a->h_k <= 0 || a->h % a->h_k != 0 || a->d % 8 != 0 || !head_dim_native(a->d)) return false;
   const int ratio = a->h / a->h_k;
   if (ratio < 2 || a->seqlen_k <= 0 || a->seqlen_q <= 0 || a->b <= 0) return false;
@@ -628,7 +677,9 @@ bool bwd_gsplit_plan(const FaBwdParams* a, GsplitPlan& pl) {
   else { while (wgs * gs < target && gs < 8 && ratio % (gs * 2) == 0) { gs *= 2; ++shift; } }   // (measured, profiles/r06_bwd_gsplit.txt: past 8 virtual heads nothing is gained; 512 uneven causal items on 256 CUs still gain 10 % from a split in two)
   if (gs < 2) return false;
   pl.gs = gs; pl.shift = shift;
-  pl.bytes = 2 * (((int64_t)a->b * a->seqlen_k * a->h_k * gs * a->d * 2 + 255) & ~(int64_t)255);
+  // (dK partials of width d, then dV partials of the value width -- = d unless FaBwdParams::d_v says otherwise)
+  pl.dk_bytes = ((int64_t)a->b * a->seqlen_k * a->h_k * gs * a->d * 2 + 255) & ~(int64_t)255;
+  pl.bytes = pl.dk_bytes + (((int64_t)a->b * a->seqlen_k * a->h_k * gs * value_dim(a->d, a->d_v) * 2 + 255) & ~(int64_t)255);
   return true;
 }
 
@@ -641,17 +692,20 @@ int launch_dkdv_any(const FaBwdParams* a, const fa::BwdK& k_in, int bf, int dk_,
     const int hk2 = a->h_k * gp.gs;
     a2.h_k = hk2;
     k.h_k = hk2; k.hk_ratio = a->h / hk2; k.kv_in_shift = gp.shift;
-    k.dk = a->workspace; k.dv = (char*)a->workspace + gp.bytes / 2;
-    k.dk_bs = k.dv_bs = (int64_t)a->seqlen_k * hk2 * a->d; k.dk_rs = k.dv_rs = (int64_t)hk2 * a->d; k.dk_hs = k.dv_hs = a->d;
+    const int dvw = value_dim(a->d, a->d_v);
+    k.dk = a->workspace; k.dv = (char*)a->workspace + gp.dk_bytes;
+    k.dk_bs = (int64_t)a->seqlen_k * hk2 * a->d; k.dk_rs = (int64_t)hk2 * a->d; k.dk_hs = a->d;
+    k.dv_bs = (int64_t)a->seqlen_k * hk2 * dvw; k.dv_rs = (int64_t)hk2 * dvw; k.dv_hs = dvw;
     fa::choose_units(a->b, hk2, 1, k.nnb, k.k_units, k.k_unit_size, k.k_unit_hpx);
   }
   int rc = -2, nw = 64;
-  if (!k.ds_ws && bwd_dkdv_schedule(&a2) == 64) rc = fa::launch_bwd_dkdv_w64(k, bf, a->d, s);
-  if (rc == -2) { nw = a->d > 128 ? 4 : 8; rc = fa::launch_bwd_dkdv(k, bf, dk_, s); }
+  const bool own_dv = own_value_dim(a->d, a->d_v);   // (never the 64-keys-per-wave kernel: it is not built for the pair)
+  if (!own_dv && !k.ds_ws && bwd_dkdv_schedule(&a2) == 64) rc = fa::launch_bwd_dkdv_w64(k, bf, a->d, s);
+  if (rc == -2) { nw = a->d > 128 ? 4 : 8; rc = own_dv ? fa::launch_bwd_dkdv_dv(k, bf, a->d, a->d_v, s) : fa::launch_bwd_dkdv(k, bf, dk_, s); }
   fa::last_schedule().bwd_dkdv_nw = nw;
   if (rc == 0 && split) {
     rc = fa::launch_bwd_gsum(k.dk, k_in.dk, bf, a->b, a->seqlen_k, a->h_k, gp.gs, a->d, k_in.dk_bs, k_in.dk_rs, k_in.dk_hs, s);
-    if (rc == 0) rc = fa::launch_bwd_gsum(k.dv, k_in.dv, bf, a->b, a->seqlen_k, a->h_k, gp.gs, a->d, k_in.dv_bs, k_in.dv_rs, k_in.dv_hs, s);
+    if (rc == 0) rc = fa::launch_bwd_gsum(k.dv, k_in.dv, bf, a->b, a->seqlen_k, a->h_k, gp.gs, value_dim(a->d, a->d_v), k_in.dv_bs, k_in.dv_rs, k_in.dv_hs, s);
   }
   return rc;
 }
@@ -768,11 +822,12 @@ int do_bwd(const FaBwdParams* a, void* stream, bool varlen) {
     if (rc != -2) return fail(FA_ERR_LAUNCH, "backward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     k.fuse_delta = 0;
   }
-  int rc = fa::launch_bwd_delta(k, bf, dk_, s);
+  const bool own_dv = own_value_dim(a->d, a->d_v);   // q / k 192, v / o 128: the 256-pitch kernels with a value width of their own
+  int rc = own_dv ? fa::launch_bwd_delta_dv(k, bf, a->d, a->d_v, s) : fa::launch_bwd_delta(k, bf, dk_, s);
   if (rc == 0) {
     rc = launch_dkdv_any(a, k, bf, dk_, s);
   }
-  if (rc == 0) rc = fa::launch_bwd_dq(k, bf, dk_, s);
+  if (rc == 0) rc = own_dv ? fa::launch_bwd_dq_dv(k, bf, a->d, a->d_v, s) : fa::launch_bwd_dq(k, bf, dk_, s);
   if (rc == 0) { fa::last_schedule().bwd_spill = 0; fa::last_schedule().bwd_list = (k.q_list != nullptr) + 2 * (k.k_list != nullptr); }
   if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no backward kernel for head dim %d", a->d);
   if (rc != 0) return fail(FA_ERR_LAUNCH, "backward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -790,6 +845,7 @@ int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool va
   if (a->b <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "batch size must be positive");
   if (a->h <= 0 || a->h_k <= 0 || a->h % a->h_k != 0)
     return fail(FA_ERR_INVALID_ARGUMENT, "Number of heads in key/value must divide number of heads in query");
+  if (int rc = check_value_dim(fn, a->d, a->d_v, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, false, true)) return rc;
   if (a->d != 64 && a->d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
   if (a->softcap < 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "softcap must be non-negative");
   if (a->softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: softcap is not supported on the fp8 path", fn);
@@ -860,6 +916,7 @@ int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool va
     f8.v_descale = f->v_descale; f8.v_bs = f->v_descale_batch_stride; f8.v_hs = f->v_descale_head_stride;
   }
   const int rc = fa::launch_fwd_fp8(k, f8, a->d, (hipStream_t)stream);
+  if (rc == 0) fa::last_schedule().dv = a->d;
   if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
   if (rc == -3) return fail(FA_ERR_UNSUPPORTED, "k/v row stride too large: one 64-key tile (64 * row_stride bytes) must span less than 2 GiB");
   if (rc != 0) return fail(FA_ERR_LAUNCH, "forward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -877,6 +934,7 @@ int do_fwd_kvcache_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream)
   if (a->b <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "batch size must be positive");
   if (a->h <= 0 || a->h_k <= 0 || a->h % a->h_k != 0)
     return fail(FA_ERR_INVALID_ARGUMENT, "Number of heads in key/value must divide number of heads in query");
+  if (int rc = check_value_dim(fn, a->d, a->d_v, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, false, true)) return rc;
   if (a->d != 64 && a->d != 128) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
   if (a->softcap < 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "softcap must be non-negative");
   if (a->softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: softcap is not supported on the fp8 path", fn);
@@ -951,6 +1009,7 @@ int do_fwd_kvcache_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream)
     f8.v_descale = f->v_descale; f8.v_bs = f->v_descale_batch_stride; f8.v_hs = f->v_descale_head_stride;
   }
   int rc = fa::launch_fwd_fp8_kv(k, f8, a->d, (hipStream_t)stream);
+  if (rc == 0) fa::last_schedule().dv = a->d;
   if (rc == 0 && k.n_splits > 1) rc = fa::launch_splitkv_combine(k, 1, a->d, (hipStream_t)stream);   // (the partials are fp32, o is bf16)
   if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "%s: head dim %d is not built (fp8 kernels: 64 and 128)", fn, a->d);
   if (rc == -3) return fail(FA_ERR_UNSUPPORTED, "k/v row stride too large: one 64-key tile (64 * row_stride bytes) must span less than 2 GiB");
@@ -975,7 +1034,7 @@ const char* fa_last_error(void) { return g_err; }
 void fa_knobs_reload(void) { g_knobs.store(read_knobs(), std::memory_order_release); }
 int fa_last_schedule(int32_t* out, int n) {
   const fa::LastSchedule& ls = fa::last_schedule();
-  const int32_t v[FA_SCHEDULE_FIELDS] = {ls.fwd_kernel, ls.fwd_nw, ls.fwd_feat, ls.fwd_splits, ls.fwd_list, ls.d, ls.bf16, ls.bwd_dq_nw, ls.bwd_list, ls.bwd_spill, ls.fwd_pack, ls.bwd_dkdv_nw};
+  const int32_t v[FA_SCHEDULE_FIELDS] = {ls.fwd_kernel, ls.fwd_nw, ls.fwd_feat, ls.fwd_splits, ls.fwd_list, ls.d, ls.bf16, ls.bwd_dq_nw, ls.bwd_list, ls.bwd_spill, ls.fwd_pack, ls.bwd_dkdv_nw, ls.dv};
   for (int i = 0; i < n && i < FA_SCHEDULE_FIELDS; ++i) out[i] = v[i];
   return FA_SCHEDULE_FIELDS;
 }
@@ -984,6 +1043,9 @@ const char* fa_last_kernel_name(void) { return fa::last_schedule().name; }
 int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true)) return rc;
+  if (int rc = check_value_dim("fa_fwd_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, a->randval, a->block_table, a->leftpad_k,
+                               a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;
+  if (own_value_dim(a->d, a->d_v)) return 4;   // fa_fwd_dv_kernel: 4 waves x 32 rows
   int causal = a->is_causal, wl = a->window_left, wr = a->window_right;
   normalize_window(a->seqlen_q, a->seqlen_k, a->alibi_slopes != nullptr, causal, wl, wr);
   int nw = fwd_schedule_nw(a, wl, wr);
@@ -998,6 +1060,7 @@ int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
 int fa_bwd_dq_schedule_query(const FaBwdParams* a) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap)) return rc;
+  if (int rc = check_value_dim("fa_bwd_dq_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, nullptr, nullptr, nullptr, false, false)) return rc;
   return bwd_dq_schedule(a);
 }
 
@@ -1090,6 +1153,10 @@ int64_t fa_fwd_workspace_bytes(const FaFwdParams* params) {
   if (!params) return 0;
   if (params->cu_seqlens_q && params->dtype == FA_DTYPE_FP8_E4M3)  // fa_varlen_fwd_fp8: 128-row blocks
     return (varlen_list_entries(params, 128) > 0) ? (varlen_list_entries(params, 128) + 1) * 8 : 0;
+  if (params->cu_seqlens_q && own_value_dim(params->d, params->d_v)) {  // fa_fwd_dv_kernel: 128-row blocks
+    const int64_t entries = varlen_list_entries(params, 128, kDvListMinDense);
+    return entries > 0 ? (entries + 1) * 8 : 0;
+  }
   if (params->cu_seqlens_q) {  // varlen forward: the work list of an uneven packed batch
     int causal = params->is_causal, wl = params->window_left, wr = params->window_right;
     normalize_window(params->seqlen_q, params->seqlen_k, params->alibi_slopes != nullptr, causal, wl, wr);

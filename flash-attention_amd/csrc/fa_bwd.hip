@@ -59,7 +59,9 @@ static __device__ const uint4 fa_zero_chunk_bwd = {0u, 0u, 0u, 0u};
 // delta[b,h,i] = sum_d dO[i,d] * O[i,d]   (reference flash_bwd_preprocess_kernel.h:24-51, dropout off)
 // ------------------------------------------------------------------------------------------------
 // (D, DV): tile pitch and head dimension present in memory, as in fa_fwd_kernel (fa_fwd.hip); DV < D = trimmed head dims 32 / 96 / 192
-template <typename E, int D, int DV>
+// DVV: width of the value side (o, dout; v and dv in the kernels below) when it differs from the q / k head dim DV (FaBwdParams::d_v: q / k 192, v / o 128);
+// columns >= DVV of the value-side tensors are never read and never written
+template <typename E, int D, int DV, int DVV = DV>
 __global__ void __launch_bounds__(256) fa_bwd_delta_kernel(const BwdK p) {
   using V8 = typename ElemTraits<E>::v8;
   constexpr int LPR = D / 8;        // lanes per row (a power of two; lanes past DV / 8 add nothing)
@@ -78,7 +80,7 @@ __global__ void __launch_bounds__(256) fa_bwd_delta_kernel(const BwdK p) {
   const int row = blockIdx.x * ROWS + threadIdx.x / LPR;
   const int c = threadIdx.x % LPR;
   float acc = 0.f;
-  if (row < sq && c < (p.d_chunks > 0 ? p.d_chunks : DV / 8)) {
+  if (row < sq && c < (p.d_chunks > 0 ? p.d_chunks : DVV / 8)) {
     const E* dop = (const E*)p.dout + do_boff + (row0 + row) * p.do_rs + (int64_t)h * p.do_hs + c * 8;
     const E* op = (const E*)p.o + o_boff + (row0 + row) * p.o_rs + (int64_t)h * p.o_hs + c * 8;
     const V8 a = bitcast_u32x4<V8>(*reinterpret_cast<const u32x4*>(dop));
@@ -128,7 +130,7 @@ __global__ void __launch_bounds__(256) fa_bwd_gsum_kernel(const E* __restrict__ 
 // ------------------------------------------------------------------------------------------------
 // The kernel's text is a device function so that the fused backward (fa_bwd_fused_kernel below, FUSED = true) can run the dQ contractions of finished
 // query blocks behind it in the same workgroup; `bid` = the workgroup's position in the 1-D grid.
-template <typename E, int D, int DV, int FEAT, bool FUSED>
+template <typename E, int D, int DV, int FEAT, bool FUSED, int DVV = DV>
 static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int bid) {
   constexpr bool XFORM = (FEAT & (FEAT_CAP | FEAT_ALIBI)) != 0;  // scores pass through the scaled domain
   constexpr bool F_CAP = (FEAT & FEAT_CAP) != 0, F_ALIBI = (FEAT & FEAT_ALIBI) != 0, F_DROP = (FEAT & FEAT_DROP) != 0;
@@ -143,6 +145,11 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
   constexpr int CPR = D / 8, ROW_BYTES = D * 2;
   constexpr int KS = DV / 16, DB = DV / 32, CV = DV / 8;   // k-steps / output blocks / 16-B chunks that exist
   static_assert(DV % 32 == 0 && DV <= D && 2 * DV >= D, "DV: a multiple of 32 in [D/2, D]");
+  // value side of its own width (DVV < DV): dP = dO.V^T contracts over KSV k-steps, dV has DBV output blocks; the V block, the dO tiles and their fragments keep
+  // the pitch D, the chunks behind DVV are zero-filled (V) or re-fetch chunk 0 (dO) and are never read from LDS; S, dK and the Q / K side stay at DV
+  constexpr int KSV = DVV / 16, DBV = DVV / 32, CVV = DVV / 8;
+  static_assert(DVV % 32 == 0 && DVV <= DV, "DVV: a multiple of 32, at most DV");
+  static_assert(DVV == DV || (FEAT & FEAT_ALL) == FEAT_NONE, "a value width of its own is built for plain attention only");
   constexpr int VBLK_BYTES = BNK * ROW_BYTES;
   constexpr int QT_BYTES = BMQ * ROW_BYTES;
   // PRE (plain variant): the matrix pipe does the two per-element subtractions.  This wave's K fragments are multiplied by
@@ -222,6 +229,7 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
   // Q / dO tiles from a page of zeros) and are not stored
   const int cvr = p.d_chunks > 0 ? p.d_chunks : CV;
   const bool bounded = cvr < CV;
+  const int cvr_v = DVV < DV ? CVV : cvr;   // chunks of a v / dv row that exist
   const E* zsrc = (const E*)&fa_zero_chunk_bwd;
   // K fragments (B operand of S = Q.K^T): lane = key, 8 consecutive d per k-step
   V8 kf[KS];
@@ -243,7 +251,7 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
     for (int i = 0; i < LDV; ++i) {
       const int idx = tid + i * NT;
       const int row = idx / CPR, ch = idx % CPR;
-      const u32x4 x = ld_global_16B(vp + (int64_t)(n0 + row) * p.v_rs + ch * 8, n0 + row < sk && ch < cvr);
+      const u32x4 x = ld_global_16B(vp + (int64_t)(n0 + row) * p.v_rs + ch * 8, n0 + row < sk && ch < cvr_v);
       *(u32x4 FA_LDS*)(lds + OFF_V + tile_off<D>(row, ch)) = x;
     }
   }
@@ -285,7 +293,7 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
       int c = pc ^ swz16<D>(row);
       if (DV < D) c = c < CV ? c : 0;  // columns past the head dimension are never read from LDS: fetch something that exists
       const E* qsrc = qp + (int64_t)grow * p.q_rs + c * 8;
-      const E* dsrc = dop + (int64_t)grow * p.do_rs + c * 8;
+      const E* dsrc = dop + (int64_t)grow * p.do_rs + (DVV < DV ? (c < CVV ? c : 0) : c) * 8;
       if (bounded && c >= cvr) { qsrc = zsrc; dsrc = zsrc; }
       lds_dma_16B(qsrc, lds + OFF_Q + buf * QT_BYTES + idx * 1024);
       lds_dma_16B(dsrc, lds + OFF_DO + buf * QT_BYTES + idx * 1024);
@@ -379,6 +387,7 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
     }
     auto rd = [&](int j) __attribute__((always_inline)) {
       const int ks = j >> 1;
+      if ((j & 1) && ks >= KSV) return;   // (a dP op behind the value width: nothing to read)
       if ((j & 1) == 0) {
         ra[j % PF] = *(const u32x4 FA_LDS*)(unsigned long)(unsigned)((QB_OFF + sub) + (k0p ^ (ks << 5)));   // (byte offsets, not lds + ..: the segment base
                                                                                                               // is 0 by construction, and as a pointer add it costs a v_add per read)
@@ -397,11 +406,12 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
       // hipcc models the explicit wait and emits none in front of the odd op.
       if ((j & 1) == 0 && j + 1 < NOPS) {
         int out = 0;
-        for (int g = j + 2; g <= j + PF - 1 && g < NOPS; ++g) out += (g & 1) ? 2 : 1;
+        for (int g = j + 2; g <= j + PF - 1 && g < NOPS; ++g) out += (g & 1) ? ((g >> 1) < KSV ? 2 : 0) : 1;
         wait_lgkm_le(out);
       }
       __builtin_amdgcn_sched_barrier(0);  // keep the prefetch above this op's MFMA
       const int ks = j >> 1;
+      if ((j & 1) && ks >= KSV) continue;
       f32x16 c = (j & 1) ? dp : s;
       if (j < 2) {
         if ((j & 1) ? PRE_D : PRE) {
@@ -534,6 +544,7 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
     const int t0p = opaque(tr_base[0]), t1p = opaque(tr_base[1]);
     auto rd = [&](int i) __attribute__((always_inline)) {
       const int db = (i >> 1) % DB, t = i / (2 * DB);
+      if ((i & 1) == 0 && db >= DBV) return;   // (a dV block behind the value width)
       const int base = ((i & 1) ? QB_OFF : DOB_OFF) + sub + 16 * t * ROW_BYTES;
       tlo[i % PFT] = lds_read_tr16((const char FA_LDS*)(unsigned long)(unsigned)(base + (t0p ^ (db << 6))));
       thi[i % PFT] = lds_read_tr16((const char FA_LDS*)(unsigned long)(unsigned)(base + (t1p ^ (db << 6))));
@@ -546,11 +557,12 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
       if (i + PFT - 1 < NOPS) rd(i + PFT - 1);
       if ((i & 1) == 0 && i + 1 < NOPS) {   // (two transpose reads per op)
         int out = 0;
-        for (int g = i + 2; g <= i + PFT - 1 && g < NOPS; ++g) out += 2;
+        for (int g = i + 2; g <= i + PFT - 1 && g < NOPS; ++g) out += ((g & 1) == 0 && (g >> 1) % DB >= DBV) ? 0 : 2;
         wait_lgkm_le(out);
       }
       __builtin_amdgcn_sched_barrier(0);
       const int db = (i >> 1) % DB, t = i / (2 * DB);
+      if ((i & 1) == 0 && db >= DBV) continue;
       if ((i & 1) == 0) dv_acc[db] = T::mfma(combine_tr<V8>(tlo[i % PFT], thi[i % PFT]), pfrag[t], dv_acc[db]);
       else dk_acc[db] = T::mfma(combine_tr<V8>(tlo[i % PFT], thi[i % PFT]), dsfrag[t], dk_acc[db]);
     }
@@ -626,12 +638,12 @@ static __device__ __forceinline__ void fa_bwd_dkdv_body(const BwdK& p, const int
   E* dvtile = (E*)p.dv + dv_boff + (k_row0 + wk0) * p.dv_rs + (int64_t)hk * p.dv_hs;
   char FA_LDS* stage = lds + wave * 32 * (ROW_BYTES + 16);
   store_tile_via_lds<E, D, DV>(stage, dk_acc, p.scale, dktile, p.dk_rs, sk - wk0, lane, cvr);
-  store_tile_via_lds<E, D, DV>(stage, dv_acc, dv_scale, dvtile, p.dv_rs, sk - wk0, lane, cvr);
+  store_tile_via_lds<E, D, DV>(stage, dv_acc, dv_scale, dvtile, p.dv_rs, sk - wk0, lane, cvr_v);   // (blocks >= DBV hold zeros and are not stored)
 }
 
-template <typename E, int D, int DV, int FEAT>
+template <typename E, int D, int DV, int FEAT, int DVV = DV>
 __global__ void __launch_bounds__(D > 128 ? 256 : 512, D > 128 ? 1 : 2) fa_bwd_dkdv_kernel(const BwdK p) {
-  fa_bwd_dkdv_body<E, D, DV, FEAT, false>(p, blockIdx.x);
+  fa_bwd_dkdv_body<E, D, DV, FEAT, false, DVV>(p, blockIdx.x);
 }
 
 #if FA_BWD_PART == 0 || FA_BWD_PART == 3
@@ -897,7 +909,7 @@ int launch_bwd_fused(const BwdK& p, int dtype_bf16, int d, hipStream_t stream) {
 // ------------------------------------------------------------------------------------------------
 // dQ
 // ------------------------------------------------------------------------------------------------
-template <typename E, int D, int DV, int NW, int FEAT>
+template <typename E, int D, int DV, int NW, int FEAT, int DVV = DV>
 __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(const BwdK p) {
   constexpr bool XFORM = (FEAT & (FEAT_CAP | FEAT_ALIBI)) != 0;
   constexpr bool F_CAP = (FEAT & FEAT_CAP) != 0, F_ALIBI = (FEAT & FEAT_ALIBI) != 0, F_DROP = (FEAT & FEAT_DROP) != 0;
@@ -909,6 +921,9 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(con
   constexpr int CPR = D / 8, ROW_BYTES = D * 2, TILE_BYTES = BN * ROW_BYTES;
   constexpr int KS = DV / 16, DB = DV / 32, CV = DV / 8;
   static_assert(DV % 32 == 0 && DV <= D && 2 * DV >= D, "DV: a multiple of 32 in [D/2, D]");
+  // value side of its own width (see fa_bwd_dkdv_body): dP^T = V.dO^T contracts over KSV k-steps; chunks >= CVV of v / dout are never fetched
+  constexpr int KSV = DVV / 16, CVV = DVV / 8;
+  static_assert(DVV % 32 == 0 && DVV <= DV && (DVV == DV || FEAT == FEAT_NONE), "DVV: a multiple of 32, at most DV; plain attention only");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char FA_LDS* lds = (char FA_LDS*)smem;  // K0 | K1 | V0 | V1
@@ -991,7 +1006,7 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(con
         int c = (lane % CPR) ^ swz16<D>(row);
         if (DV < D) c = c < CV ? c : 0;
         const int grow = min(m0 + row, sq - 1);
-        const E* src = (which ? (dosrc + (int64_t)grow * p.do_rs) : (qsrc + (int64_t)grow * p.q_rs)) + c * 8;
+        const E* src = (which ? (dosrc + (int64_t)grow * p.do_rs + (DVV < DV ? (c < CVV ? c : 0) : c) * 8) : (qsrc + (int64_t)grow * p.q_rs + c * 8));
         if (bounded && c >= cvr) src = zsrc;
         lds_dma_16B(src, lds + (wave * QDPW + i) * 1024);
       }
@@ -1024,7 +1039,7 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(con
       if (DV < D) c = c < CV ? c : 0;
       const int key = min(n * BN + row, sk - 1);
       const E* ks_ = kp + (int64_t)key * p.k_rs + c * 8;
-      const E* vs_ = vp + (int64_t)key * p.v_rs + c * 8;
+      const E* vs_ = vp + (int64_t)key * p.v_rs + (DVV < DV ? (c < CVV ? c : 0) : c) * 8;
       if (bounded && c >= cvr) { ks_ = zsrc; vs_ = zsrc; }
       lds_dma_16B(ks_, lds + buf * TILE_BYTES + idx * 1024);
       lds_dma_16B(vs_, lds + (2 + buf) * TILE_BYTES + idx * 1024);
@@ -1080,6 +1095,7 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(con
           const int k0p = opaque(k0);
           auto rd = [&](int j) __attribute__((always_inline)) {
             const int ks = j >> 1;
+            if ((j & 1) && ks >= KSV) return;   // (a dP op behind the value width)
             ra[j % PF] = *(const u32x4 FA_LDS*)(unsigned long)(unsigned)((((j & 1) ? VB_OFF : KB_OFF) + sub) + (k0p ^ (ks << 5)));
           };
 #pragma unroll
@@ -1089,6 +1105,7 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_bwd_dq_kernel(con
             if (j + PF - 1 < NOPS) rd(j + PF - 1);
             __builtin_amdgcn_sched_barrier(0);
             const int ks = j >> 1;
+            if ((j & 1) && ks >= KSV) continue;
             f32x16 c = (j & 1) ? dp : s;
             if (j < 2) {
 #pragma unroll
@@ -1195,19 +1212,19 @@ int bwd_block_m(int nw);
 #if FA_BWD_PART == 0 || FA_BWD_PART == 1
 int bwd_block_n(int d) { return d > 128 ? 128 : 256; }
 
-template <typename E, int D, int DV>
+template <typename E, int D, int DV, int DVV = DV>
 static int launch_delta_t(const BwdK& p, hipStream_t stream) {
   constexpr int ROWS = 256 / (D / 8);
   dim3 grid((p.sq + ROWS - 1) / ROWS, p.h, p.b);
-  hipLaunchKernelGGL((fa_bwd_delta_kernel<E, D, DV>), grid, dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((fa_bwd_delta_kernel<E, D, DV, DVV>), grid, dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-template <typename E, int D, int DV, int FEAT>
+template <typename E, int D, int DV, int FEAT, int DVV = DV>
 static int launch_dkdv_a(const BwdK& p, hipStream_t stream) {
   constexpr int NWK = D > 128 ? 4 : 8, BMQ = D > 128 ? 32 : 64;
   constexpr int smem = NWK * 32 * D * 2 + 4 * BMQ * D * 2 + 4 * BMQ * 4;
-  auto kern = fa_bwd_dkdv_kernel<E, D, DV, FEAT>;
+  auto kern = fa_bwd_dkdv_kernel<E, D, DV, FEAT, DVV>;
   static std::atomic<unsigned long long> attr_mask{0};
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;   // (operand reads address LDS by byte offset: the dynamic segment starts at 0)
   const long long total = p.k_list ? (long long)p.k_bound * p.h_k : units_grid(p.k_units, p.k_unit_size);
@@ -1239,10 +1256,10 @@ static int launch_dkdv_t(const BwdK& p, hipStream_t stream) {
 
 #endif  // FA_BWD_PART == 0 || FA_BWD_PART == 1
 #if FA_BWD_PART == 0 || FA_BWD_PART == 2
-template <typename E, int D, int DV, int NW, int FEAT>
+template <typename E, int D, int DV, int NW, int FEAT, int DVV = DV>
 static int launch_dq_nw(const BwdK& p, hipStream_t stream) {
   constexpr int smem = 4 * 64 * D * 2 + NW * 32 * 16;  // K/V double buffers (+ the row padding of the staged dQ epilogue)
-  auto kern = fa_bwd_dq_kernel<E, D, DV, NW, FEAT>;
+  auto kern = fa_bwd_dq_kernel<E, D, DV, NW, FEAT, DVV>;
   static std::atomic<unsigned long long> attr_mask{0};
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;   // (operand reads address LDS by byte offset: the dynamic segment starts at 0)
   const long long total = p.q_list ? (long long)p.q_bound * p.h : units_grid(p.q_units, p.q_unit_size);
@@ -1298,6 +1315,15 @@ int launch_bwd_gsum(const void* src, void* dst, int dtype_bf16, int b, int sk, i
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_bwd_dkdv(const BwdK& p, int dtype_bf16, int d, hipStream_t stream) { FA_BWD_DISPATCH(launch_dkdv_t) }
+// q / k head dim 192, value width 128 (FaBwdParams::d_v): plain attention, every score scaled in fp32 (FEAT_EXACT)
+int launch_bwd_delta_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream) {
+  if (d != 192 || dv != 128) return -2;
+  return dtype_bf16 ? launch_delta_t<__bf16, 256, 192, 128>(p, stream) : launch_delta_t<_Float16, 256, 192, 128>(p, stream);
+}
+int launch_bwd_dkdv_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream) {
+  if (d != 192 || dv != 128 || p.softcap > 0.f || p.alibi || p.rng || p.ds_ws || p.d_chunks > 0) return -2;
+  return dtype_bf16 ? launch_dkdv_a<__bf16, 256, 192, FEAT_EXACT, 128>(p, stream) : launch_dkdv_a<_Float16, 256, 192, FEAT_EXACT, 128>(p, stream);
+}
 #endif
 #if FA_BWD_PART == 0 || FA_BWD_PART == 2
 int launch_bwd_dq(const BwdK& p, int dtype_bf16, int d, hipStream_t stream) {
@@ -1309,6 +1335,11 @@ int launch_bwd_dq(const BwdK& p, int dtype_bf16, int d, hipStream_t stream) {
     if (rc != -2) { ls.bwd_dq_nw = 64; return rc; }
   }
   FA_BWD_DISPATCH(launch_dq_t)
+}
+int launch_bwd_dq_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream) {
+  if (d != 192 || dv != 128 || p.softcap > 0.f || p.alibi || p.rng || p.d_chunks > 0) return -2;
+  last_schedule().bwd_dq_nw = 4;
+  return dtype_bf16 ? launch_dq_nw<__bf16, 256, 192, 4, FEAT_NONE, 128>(p, stream) : launch_dq_nw<_Float16, 256, 192, 4, FEAT_NONE, 128>(p, stream);
 }
 #endif
 

@@ -39,7 +39,7 @@ const Knobs& knobs();
 
 // What the last fa_fwd* / fa_bwd* call of this thread launched (fa_last_schedule in the C ABI).
 struct LastSchedule {
-  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel, 5 fa_fwd_fp8_kv_kernel
+  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel, 5 fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel
   int fwd_nw;       // waves per workgroup (16 = 8-wave ping-pong)
   int fwd_feat;     // FEAT_* variant of the lock-step kernel
   int fwd_splits;   // split-KV factor
@@ -48,6 +48,7 @@ struct LastSchedule {
   int bwd_dq_nw, bwd_list, bwd_spill;
   int fwd_pack;     // query heads packed into the rows (FwdK::pack_g)
   int bwd_dkdv_nw;  // dK/dV schedule: 8 = eight waves x 32 keys (4 at head dim 256), 64 = four waves x 64 keys (fa_bwd_dkdv_w64.hip)
+  int dv;           // head dim of v / o of the last forward (= d unless the call gave v its own width)
   char name[96];
 };
 LastSchedule& last_schedule();
@@ -137,6 +138,10 @@ int launch_fwd_fp8(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
 // kernel reads them; with n_splits > 1 the caller runs launch_splitkv_combine (bf16) behind it.  Same return codes.
 int launch_fwd_fp8_kv(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
 
+// Forward for a v / o head dim of its own (fa_fwd_dv.hip): q / k head dim d = 192, v / o head dim dv = 128; 4 waves, 128 query rows and 80 KB of LDS per
+// workgroup, two workgroups per CU.  Plain attention (masks, GQA, packed batches, seqused_q / seqused_k).  -2 = pair not built.
+int launch_fwd_dv(const FwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
+
 // Backward: delta = rowsum(dO*O) pre-pass, dK/dV kernel (loops over query blocks),
 // dQ kernel (loops over key blocks).  Same return convention.
 int launch_bwd_delta(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);
@@ -144,6 +149,11 @@ int launch_bwd_gsum(const void* src, void* dst, int dtype_bf16, int b, int sk, i
 int launch_bwd_dkdv(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);
 int launch_bwd_fused(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);   // fa_bwd.hip (FA_BWD_PART=3): dK/dV + dQ = dS.K in one launch; -2 = does not apply
 int launch_bwd_dq(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);
+// The same three for a value side (v, o, dout, dv) of its own width dv < d: the 256-pitch kernels of head dim 192 with value width 128 (fa_bwd.hip, template
+// parameter DVV).  Plain attention only (dK/dV: FEAT_EXACT, 4 waves x 32 keys; dQ: 4 waves x 32 rows).  -2 = pair not built.
+int launch_bwd_delta_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
+int launch_bwd_dkdv_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
+int launch_bwd_dq_dv(const BwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
 int launch_bwd_dq_w64(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);
 int launch_bwd_dkdv_w64(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);
 int launch_bwd_c5(const BwdK& p, int dtype_bf16, int d, hipStream_t stream);   // fa_bwd_dkdv_w64.hip (FA_DKDV64_PART=2): one mixed launch of the 5-contraction backward (dK/dV items of a chunk + dQ = dS.K items of the chunk before); -2 = not covered   // fa_bwd_dkdv_w64.hip: 64 keys per wave, software-pipelined; -2 = not covered

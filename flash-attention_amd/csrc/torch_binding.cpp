@@ -45,6 +45,19 @@ int dtype_code(const Tensor& q) {
 // in between through the kernels' run-time column bound (FaFwdParams / FaBwdParams::d, fa_api.cpp: head_dim_kernel): no padded copies anywhere.
 void check_head_dim(int64_t d) { TORCH_CHECK(d <= 256, "FlashAttention only supports head dimension at most 256"); }
 
+// A v / o head dim of its own (Dv != D): one pair is built, q / k 192 with v / o 128 (FaFwdParams::d_v).  The refusals of the C ABI (fa_api.cpp
+// check_value_dim), checked on shapes and flags alone; the messages name both head dims or the argument, as the ctypes binder's do.
+void check_head_dim_pair(const char* fn, int64_t d, int64_t dv, double p_dropout, double softcap, bool alibi, bool return_softmax, bool block_table, bool leftpad_k) {
+  if (dv == d) return;
+  TORCH_CHECK(d == 192 && dv == 128, fn, ": head dims (", d, ", ", dv, "): the only built pair with a v head dim that differs from q / k is (192, 128)");
+  TORCH_CHECK(!(p_dropout > 0.0), fn, ": head dims (", d, ", ", dv, ") do not support dropout (p_dropout)");
+  TORCH_CHECK(!(softcap > 0.0), fn, ": head dims (", d, ", ", dv, ") do not support softcap");
+  TORCH_CHECK(!alibi, fn, ": head dims (", d, ", ", dv, ") do not support ALiBi (alibi_slopes)");
+  TORCH_CHECK(!return_softmax, fn, ": head dims (", d, ", ", dv, ") do not support return_softmax");
+  TORCH_CHECK(!block_table, fn, ": head dims (", d, ", ", dv, ") do not support block_table (paged KV)");
+  TORCH_CHECK(!leftpad_k, fn, ": head dims (", d, ", ", dv, ") do not support leftpad_k");
+}
+
 void common_checks(const Tensor& q, const Tensor& k, const Tensor& v, double p_dropout, const OptTensor& alibi,
                    const GenSlot& gen) {
   TORCH_CHECK(gen.is_none(), "flash-attn: the RNG `generator` argument is no longer supported and must be None; dropout (when enabled) uses the default generator of the device.");
@@ -106,16 +119,18 @@ std::vector<Tensor> mha_fwd(Tensor& q, const Tensor& k, const Tensor& v, OptTens
   TORCH_CHECK(D <= 256, "FlashAttention forward only supports head dimension at most 256");
   TORCH_CHECK(D % 8 == 0, "query, key, value, and out_ must have a head_size that is a multiple of 8");
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  const int64_t Dv = v.size(3);   // v / o may have a head dim of their own
   CHECK_SHAPE(k, B, Sk, Hk, D);
-  CHECK_SHAPE(v, B, Sk, Hk, D);
+  CHECK_SHAPE(v, B, Sk, Hk, Dv);
+  check_head_dim_pair("fwd", D, Dv, p_dropout, softcap, alibi_slopes_.has_value(), return_softmax, false, false);
   c10::DeviceGuard guard(q.device());
   if (out_.has_value()) {
     TORCH_CHECK(out_->dtype() == q.dtype(), "Output must have the same dtype as inputs");
-    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, B, Sq, H, D);
+    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, B, Sq, H, Dv);
   }
   // One query row and grouped heads: the query heads of a KV group become the rows of one block, K/V are streamed once
   // per KV head (seqlenq_ngroups_swapped, flash_api.cpp:429-437 and :531-535)
-  if (Sq == 1 && H > Hk && window_size_left < 0 && window_size_right < 0 && p_dropout == 0.0 && !alibi_slopes_.has_value() && Sk > 0) {
+  if (Sq == 1 && H > Hk && window_size_left < 0 && window_size_right < 0 && p_dropout == 0.0 && !alibi_slopes_.has_value() && Sk > 0 && Dv == D) {
     const int64_t ng = H / Hk;
     Tensor q2 = q.reshape({B, Hk, ng, D}).transpose(1, 2);
     OptTensor none;
@@ -127,7 +142,7 @@ std::vector<Tensor> mha_fwd(Tensor& q, const Tensor& k, const Tensor& v, OptTens
   check_head_dim(D);
   const Tensor &qp = q, &kp = k, &vp = v;
   Tensor out;
-  out = out_.has_value() ? *out_ : at::empty({B, Sq, H, D}, q.options());
+  out = out_.has_value() ? *out_ : at::empty({B, Sq, H, Dv}, q.options());
   Tensor lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
   Tensor rng_state = make_rng_state(q, p_dropout, B, H);
   // return_softmax: the random byte of every (query, key) pair, the ROCm backend's payload (csrc/flash_attn_ck/mha_fwd.cpp:275-279)
@@ -144,6 +159,7 @@ std::vector<Tensor> mha_fwd(Tensor& q, const Tensor& k, const Tensor& v, OptTens
     a.o_batch_stride = out.stride(0); a.o_row_stride = out.stride(1); a.o_head_stride = out.stride(2);
     set_alibi(alibi_slopes_, B, H, a.alibi_slopes, a.alibi_batch_stride);
     a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = Sq; a.seqlen_k = Sk; a.total_q = B * Sq;
+    a.d_v = Dv != D ? (int)Dv : 0;
     a.dtype = dtype_code(q);
     a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
     a.softmax_scale = (float)softmax_scale; a.softcap = (float)softcap;
@@ -198,12 +214,15 @@ std::vector<Tensor> mha_varlen_fwd(Tensor& q, const Tensor& k, const Tensor& v, 
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
   if (paged) {
     CHECK_SHAPE(k, k.size(0), k.size(1), Hk, D);
+    check_head_dim_pair("varlen_fwd", D, v.size(-1), p_dropout, softcap, alibi_slopes_.has_value(), return_softmax, true, leftpad_k_.has_value());
     TORCH_CHECK(v.sizes() == k.sizes(), "paged k / v shape mismatch");
     CHECK_SHAPE(*block_table_, B, block_table_->size(1));
   } else {
     CHECK_SHAPE(k, total_k, Hk, D);
-    CHECK_SHAPE(v, total_k, Hk, D);
+    CHECK_SHAPE(v, total_k, Hk, v.size(2));
   }
+  const int64_t Dv = v.size(-1);   // v / o may have a head dim of their own
+  check_head_dim_pair("varlen_fwd", D, Dv, p_dropout, softcap, alibi_slopes_.has_value(), return_softmax, paged, leftpad_k_.has_value());
   if (leftpad_k_.has_value()) CHECK_SHAPE(*leftpad_k_, B);
   if (seqused_k.has_value()) {
     TORCH_CHECK(seqused_k->dtype() == at::kInt, "seqused_k must have dtype int32");
@@ -215,7 +234,7 @@ std::vector<Tensor> mha_varlen_fwd(Tensor& q, const Tensor& k, const Tensor& v, 
   // One query row per sequence and grouped heads (decode over a packed batch): the query heads of a KV group become the
   // rows of one block (seqlenq_ngroups_swapped, flash_api.cpp:620-629 and :776-782); q is then ngroups rows per sequence
   if (max_seqlen_q == 1 && total_q == B && H > Hk && window_size_left < 0 && window_size_right < 0 && p_dropout == 0.0 &&
-      !alibi_slopes_.has_value() && max_seqlen_k > 0 && total_k > 0) {
+      !alibi_slopes_.has_value() && max_seqlen_k > 0 && total_k > 0 && Dv == D) {
     const int64_t ng = H / Hk;
     Tensor q2 = q.reshape({B, Hk, ng, D}).transpose(1, 2).reshape({B * ng, Hk, D});
     Tensor cu_q2 = at::arange(0, (B + 1) * ng, ng, cu_seqlens_q.options());
@@ -235,9 +254,9 @@ std::vector<Tensor> mha_varlen_fwd(Tensor& q, const Tensor& k, const Tensor& v, 
   const Tensor &qp = q, &kp = k, &vp = v;
   if (out_.has_value()) {
     TORCH_CHECK(out_->dtype() == q.dtype(), "Output must have the same dtype as inputs");
-    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, total_q, H, D);
+    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, total_q, H, Dv);
   }
-  Tensor out = out_.has_value() ? *out_ : at::empty({total_q, H, D}, q.options());
+  Tensor out = out_.has_value() ? *out_ : at::empty({total_q, H, Dv}, q.options());
   Tensor lse = at::empty({H, total_q}, q.options().dtype(at::kFloat));
   Tensor rng_state = make_rng_state(q, p_dropout, B, H);
   // varlen payload layout of the ROCm backend: (nheads, total_q, max_seqlen_k)
@@ -268,6 +287,7 @@ std::vector<Tensor> mha_varlen_fwd(Tensor& q, const Tensor& k, const Tensor& v, 
     a.seqused_k = seqused_k.has_value() ? seqused_k->data_ptr<int>() : nullptr;
     set_alibi(alibi_slopes_, B, H, a.alibi_slopes, a.alibi_batch_stride);
     a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = (int)max_seqlen_q; a.seqlen_k = (int)max_seqlen_k; a.total_q = total_q;
+    a.d_v = Dv != D ? (int)Dv : 0;
     a.dtype = dtype_code(q);
     a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
     a.softmax_scale = (float)softmax_scale; a.softcap = (float)softcap;
@@ -348,7 +368,9 @@ std::vector<Tensor> mha_bwd(const Tensor& dout, const Tensor& q, const Tensor& k
   TORCH_CHECK(D % 8 == 0, "head_size should be a multiple of 8");
   TORCH_CHECK(D <= 256, "FlashAttention backward only supports head dimension at most 256");
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
-  CHECK_SHAPE(k, B, Sk, Hk, D); CHECK_SHAPE(v, B, Sk, Hk, D); CHECK_SHAPE(out, B, Sq, H, D); CHECK_SHAPE(dout, B, Sq, H, D);
+  const int64_t Dv = v.size(3);   // the value side (v, out, dout, dv) may have a head dim of its own
+  check_head_dim_pair("bwd", D, Dv, p_dropout, softcap, alibi_slopes_.has_value(), false, false, false);
+  CHECK_SHAPE(k, B, Sk, Hk, D); CHECK_SHAPE(v, B, Sk, Hk, Dv); CHECK_SHAPE(out, B, Sq, H, Dv); CHECK_SHAPE(dout, B, Sq, H, Dv);
   CHECK_SHAPE(softmax_lse, B, H, Sq);
   c10::DeviceGuard guard(q.device());
   Tensor dq = grad_buffer(dq_, q, "dq"), dk = grad_buffer(dk_, k, "dk"), dv = grad_buffer(dv_, v, "dv");
@@ -364,6 +386,7 @@ std::vector<Tensor> mha_bwd(const Tensor& dout, const Tensor& q, const Tensor& k
   SET3(do, t.dout) SET3(q, t.q) SET3(k, t.k) SET3(v, t.v) SET3(o, t.out) SET3(dq, t.dq) SET3(dk, t.dk) SET3(dv, t.dv)
   set_alibi(alibi_slopes_, B, H, a.alibi_slopes, a.alibi_batch_stride);
   a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = Sq; a.seqlen_k = Sk; a.total_q = B * Sq; a.total_k = B * Sk;
+  a.d_v = Dv != D ? (int)Dv : 0;
   a.dtype = dtype_code(q);
   a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
   a.softmax_scale = (float)softmax_scale; a.softcap = (float)softcap; a.deterministic = deterministic;
@@ -391,7 +414,9 @@ std::vector<Tensor> mha_varlen_bwd(const Tensor& dout, const Tensor& q, const Te
   TORCH_CHECK(B > 0, "batch size must be positive");
   TORCH_CHECK(D % 8 == 0 && D <= 256, "head_size should be a multiple of 8 and at most 256");
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
-  CHECK_SHAPE(k, total_k, Hk, D); CHECK_SHAPE(v, total_k, Hk, D); CHECK_SHAPE(out, total_q, H, D); CHECK_SHAPE(dout, total_q, H, D);
+  const int64_t Dv = v.size(2);   // the value side (v, out, dout, dv) may have a head dim of its own
+  check_head_dim_pair("varlen_bwd", D, Dv, p_dropout, softcap, alibi_slopes_.has_value(), false, false, false);
+  CHECK_SHAPE(k, total_k, Hk, D); CHECK_SHAPE(v, total_k, Hk, Dv); CHECK_SHAPE(out, total_q, H, Dv); CHECK_SHAPE(dout, total_q, H, Dv);
   CHECK_SHAPE(cu_seqlens_q, B + 1); CHECK_SHAPE(cu_seqlens_k, B + 1);
   CHECK_SHAPE(softmax_lse, H, total_q);
   c10::DeviceGuard guard(q.device());
@@ -411,6 +436,7 @@ std::vector<Tensor> mha_varlen_bwd(const Tensor& dout, const Tensor& q, const Te
   set_alibi(alibi_slopes_, B, H, a.alibi_slopes, a.alibi_batch_stride);
   a.b = B; a.h = H; a.h_k = Hk; a.d = (int)D; a.seqlen_q = (int)max_seqlen_q; a.seqlen_k = (int)max_seqlen_k;
   a.total_q = total_q; a.total_k = total_k;
+  a.d_v = Dv != D ? (int)Dv : 0;
   a.dtype = dtype_code(q);
   a.is_causal = is_causal; a.window_left = (int)window_size_left; a.window_right = (int)window_size_right;
   a.softmax_scale = (float)softmax_scale; a.softcap = (float)softcap; a.deterministic = deterministic;
@@ -459,6 +485,7 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
   }
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
   const int64_t Hk = kcache.size(2);
+  TORCH_CHECK(vcache.size(-1) == D, "fwd_kvcache: head dims (", D, ", ", vcache.size(-1), "): the KV-cache path has no kernel for a v head dim that differs from q / k");
   const int64_t page = paged ? kcache.size(1) : 0;
   const int64_t Sk = paged ? block_table_->size(1) * page : kcache.size(1);
   TORCH_CHECK(B > 0, "batch size must be positive");
@@ -642,6 +669,7 @@ std::vector<Tensor> mha_fwd_fp8(const Tensor& q, const Tensor& k, const Tensor& 
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3), Sk = k.size(1), Hk = k.size(2);
   TORCH_CHECK(B > 0, "batch size must be positive");
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  TORCH_CHECK(v.size(-1) == D, "fwd_fp8: head dims (", D, ", ", v.size(-1), "): the fp8 path has no kernel for a v head dim that differs from q / k");
   CHECK_SHAPE(k, B, Sk, Hk, D);
   CHECK_SHAPE(v, B, Sk, Hk, D);
   c10::DeviceGuard guard(q.device());
@@ -682,6 +710,7 @@ std::vector<Tensor> mha_varlen_fwd_fp8(const Tensor& q, const Tensor& k, const T
   TORCH_CHECK(B > 0, "batch size must be positive");
   CHECK_SHAPE(cu_seqlens_k, B + 1);
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
+  TORCH_CHECK(v.size(-1) == D, "varlen_fwd_fp8: head dims (", D, ", ", v.size(-1), "): the fp8 path has no kernel for a v head dim that differs from q / k");
   CHECK_SHAPE(k, total_k, Hk, D);
   CHECK_SHAPE(v, total_k, Hk, D);
   c10::DeviceGuard guard(q.device());
@@ -736,6 +765,7 @@ std::vector<Tensor> mha_fwd_kvcache_fp8(const Tensor& q, const Tensor& kcache, c
   }
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
   const int64_t Hk = kcache.size(2);
+  TORCH_CHECK(vcache.size(-1) == D, "fwd_kvcache: head dims (", D, ", ", vcache.size(-1), "): the KV-cache path has no kernel for a v head dim that differs from q / k");
   const int64_t page = paged ? kcache.size(1) : 0;
   const int64_t Sk = paged ? block_table_->size(1) * page : kcache.size(1);
   TORCH_CHECK(B > 0, "batch size must be positive");

@@ -31,7 +31,7 @@ class FaFwdParams(C.Structure):
         ("is_causal", _i32), ("window_left", _i32), ("window_right", _i32),
         ("softmax_scale", _f32), ("softcap", _f32), ("seqused_k_add", _i32),
         ("cache_batch_idx", _vp), ("block_table", _vp), ("block_table_batch_stride", _i64),
-        ("page_block_size", _i32), ("num_splits", _i32), ("p_dropout", _f32), ("reserved0", _i32),
+        ("page_block_size", _i32), ("num_splits", _i32), ("p_dropout", _f32), ("d_v", _i32),
         ("rng_state", _vp), ("randval", _vp),
         ("randval_batch_stride", _i64), ("randval_head_stride", _i64), ("randval_row_stride", _i64),
         ("workspace", _vp), ("workspace_bytes", _i64), ("leftpad_k", _vp), ("seqused_q", _vp),
@@ -89,7 +89,7 @@ class FaBwdParams(C.Structure):
         ("seqlen_q", _i32), ("seqlen_k", _i32), ("total_q", _i32), ("total_k", _i32),
         ("dtype", _i32), ("is_causal", _i32), ("window_left", _i32), ("window_right", _i32),
         ("softmax_scale", _f32), ("softcap", _f32), ("deterministic", _i32),
-        ("p_dropout", _f32), ("reserved", _i32 * 3), ("rng_state", _vp), ("seqused_q", _vp), ("seqused_k", _vp),
+        ("p_dropout", _f32), ("d_v", _i32), ("reserved", _i32 * 2), ("rng_state", _vp), ("seqused_q", _vp), ("seqused_k", _vp),
     ]
 
 

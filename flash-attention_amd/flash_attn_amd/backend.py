@@ -25,8 +25,10 @@ def reload_knobs() -> None:
     _cabi.load().fa_knobs_reload()
 
 
-_SCHED_FIELDS = ("fwd_kernel", "fwd_nw", "fwd_feat", "fwd_splits", "fwd_list", "d", "bf16", "bwd_dq_nw", "bwd_list", "bwd_spill", "fwd_pack", "bwd_dkdv_nw")
-FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel", 5: "fa_fwd_fp8_kv_kernel"}
+_SCHED_FIELDS = ("fwd_kernel", "fwd_nw", "fwd_feat", "fwd_splits", "fwd_list", "d", "bf16", "bwd_dq_nw", "bwd_list", "bwd_spill", "fwd_pack", "bwd_dkdv_nw", "dv")
+FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel", 5: "fa_fwd_fp8_kv_kernel",
+                    6: "fa_fwd_dv_kernel"}
+HEAD_DIM_PAIRS = ((192, 128),)  # (q / k head dim, v / o head dim) pairs built besides Dv = D (csrc/fa_api.cpp check_value_dim)
 
 
 def last_schedule() -> dict:
@@ -67,6 +69,20 @@ def _check_d(d: int) -> None:
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def check_head_dim_pair(fn: str, d: int, dv: int, *, p_dropout=0.0, softcap=0.0, alibi_slopes=None, return_softmax=False, block_table=None,
+                        leftpad_k=None) -> None:
+    """A v / o head dim of its own (Dv != D): the refusals of the C ABI (fa_api.cpp check_value_dim) on shapes and flags alone, so that they also hold
+    under fake tensors.  Raises RuntimeError naming both head dims or the argument."""
+    if dv == d:
+        return
+    if (d, dv) not in HEAD_DIM_PAIRS:
+        raise RuntimeError(f"{fn}: head dims ({d}, {dv}): the only built pair with a v head dim that differs from q / k is (192, 128)")
+    for bad, what in ((p_dropout > 0.0, "dropout (p_dropout)"), (softcap > 0.0, "softcap"), (alibi_slopes is not None, "ALiBi (alibi_slopes)"),
+                      (bool(return_softmax), "return_softmax"), (block_table is not None, "block_table (paged KV)"), (leftpad_k is not None, "leftpad_k")):
+        if bad:
+            raise RuntimeError(f"{fn}: head dims ({d}, {dv}) do not support {what}")
 
 
 def _common_checks(q, k, v, p_dropout, alibi_slopes, gen_):
@@ -125,15 +141,17 @@ def fwd(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal, windo
         raise RuntimeError("query, key, value, and out_ must have a head_size that is a multiple of 8")
     if H % Hk != 0:
         raise RuntimeError("Number of heads in key/value must divide number of heads in query")
-    if tuple(k.shape) != (B, Sk, Hk, D) or tuple(v.shape) != (B, Sk, Hk, D):
+    Dv = v.shape[-1]   # v / o may have a head dim of their own (HEAD_DIM_PAIRS)
+    if tuple(k.shape) != (B, Sk, Hk, D) or tuple(v.shape) != (B, Sk, Hk, Dv):
         raise RuntimeError("key/value shape mismatch")
+    check_head_dim_pair("fwd", D, Dv, p_dropout=p_dropout, softcap=softcap, alibi_slopes=alibi_slopes_, return_softmax=return_softmax)
     if out_ is not None:
-        if out_.dtype != q.dtype or tuple(out_.shape) != (B, Sq, H, D) or out_.stride(-1) != 1:
-            raise RuntimeError("out_ must have the same dtype/shape as q and a contiguous last dimension")
+        if out_.dtype != q.dtype or tuple(out_.shape) != (B, Sq, H, Dv) or out_.stride(-1) != 1:
+            raise RuntimeError("out_ must have the same dtype as q, shape (batch, seqlen_q, nheads, v's head dim) and a contiguous last dimension")
     # One query row and grouped heads: the query heads of a KV group become the rows of one block, K/V are streamed once
     # per KV head (seqlenq_ngroups_swapped, flash_api.cpp:429-437 and :531-535)
     if (Sq == 1 and H > Hk and window_size_left < 0 and window_size_right < 0 and p_dropout == 0.0 and alibi_slopes_ is None
-            and Sk > 0):
+            and Sk > 0 and Dv == D):   # (Dv != D: the kernel of that shape takes the query heads as they are)
         ng = H // Hk
         o2, l2, p2, r2 = fwd(q.reshape(B, Hk, ng, D).transpose(1, 2), k, v, None, None, 0.0, softmax_scale, False, -1, -1,
                              softcap, False, None)
@@ -144,7 +162,7 @@ def fwd(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal, windo
         return [out, l2.reshape(B, H, 1), p2, r2]
     _check_d(D)
     qp, kp, vp = q, k, v
-    out = out_ if out_ is not None else torch.empty((B, Sq, H, D), dtype=q.dtype, device=q.device)
+    out = out_ if out_ is not None else torch.empty((B, Sq, H, Dv), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     rng_state = _new_rng_state(q.device, p_dropout, B, H)
     # return_softmax: the random byte of every (query, key) pair, the ROCm backend's payload (mha_fwd.cpp:275-279)
@@ -163,6 +181,7 @@ def fwd(q, k, v, out_, alibi_slopes_, p_dropout, softmax_scale, is_causal, windo
         a.o_batch_stride, a.o_row_stride, a.o_head_stride = out.stride(0), out.stride(1), out.stride(2)
         a.alibi_slopes, a.alibi_batch_stride = _ptr(alibi), alibi_bs
         a.b, a.h, a.h_k, a.d = B, H, Hk, D
+        a.d_v = Dv if Dv != D else 0
         a.seqlen_q, a.seqlen_k, a.total_q = Sq, Sk, B * Sq
         a.dtype = _dtype_code(q)
         a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)
@@ -220,10 +239,17 @@ def varlen_fwd(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, leftpad_k_,
         raise RuntimeError("head_size must be a multiple of 8 and at most 256")
     if H % Hk != 0:
         raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    Dv = v.shape[-1]   # v / o may have a head dim of their own (HEAD_DIM_PAIRS)
+    check_head_dim_pair("varlen_fwd", D, Dv, p_dropout=p_dropout, softcap=softcap, alibi_slopes=alibi_slopes_, return_softmax=return_softmax,
+                        block_table=block_table_, leftpad_k=leftpad_k_)
+    if Dv != D and (k.shape[-1] != D or tuple(v.shape[:-1]) != tuple(k.shape[:-1])):
+        raise RuntimeError("key/value shape mismatch")
+    if out_ is not None and Dv != D and (out_.dtype != q.dtype or tuple(out_.shape) != (total_q, H, Dv) or out_.stride(-1) != 1):
+        raise RuntimeError("out_ must have the same dtype as q, shape (total_q, nheads, v's head dim) and a contiguous last dimension")
     # One query row per sequence and grouped heads (decode over a packed batch): the query heads of a KV group become the
     # rows of one block (seqlenq_ngroups_swapped, flash_api.cpp:620-629 and :776-782); q is then ngroups rows per sequence
     if (max_seqlen_q == 1 and total_q == B and H > Hk and window_size_left < 0 and window_size_right < 0 and p_dropout == 0.0
-            and alibi_slopes_ is None and max_seqlen_k > 0 and total_k > 0):
+            and alibi_slopes_ is None and max_seqlen_k > 0 and total_k > 0 and Dv == D):
         ng = H // Hk
         q2 = q.reshape(B, Hk, ng, D).transpose(1, 2).reshape(B * ng, Hk, D)
         cu_q2 = torch.arange(0, (B + 1) * ng, ng, dtype=torch.int32, device=q.device)
@@ -242,7 +268,7 @@ def varlen_fwd(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, leftpad_k_,
     _check_dev(seqused_q)
     _check_d(D)
     qp, kp, vp = q, k, v
-    out = out_ if out_ is not None else torch.empty((total_q, H, D), dtype=q.dtype, device=q.device)
+    out = out_ if out_ is not None else torch.empty((total_q, H, Dv), dtype=q.dtype, device=q.device)
     lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
     rng_state = _new_rng_state(q.device, p_dropout, B, H)
     # varlen payload layout of the ROCm backend: (nheads, total_q, max_seqlen_k) (mha_varlen_fwd.cpp)
@@ -272,6 +298,7 @@ def varlen_fwd(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, seqused_k, leftpad_k_,
         a.seqused_q = _ptr(seqused_q)
         a.alibi_slopes, a.alibi_batch_stride = _ptr(alibi), alibi_bs
         a.b, a.h, a.h_k, a.d = B, H, Hk, D
+        a.d_v = Dv if Dv != D else 0
         a.seqlen_q, a.seqlen_k, a.total_q = int(max_seqlen_q), int(max_seqlen_k), total_q
         a.dtype = _dtype_code(q)
         a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)
@@ -322,6 +349,8 @@ def fwd_fp8(q, k, v, out_, q_descale, k_descale, v_descale, softmax_scale, is_ca
     """FP8 forward (C ABI fa_fwd_fp8): q (B,Sq,H,D), k/v (B,Sk,Hk,D) float8_e4m3fn, optional fp32 (B,Hk) descales -> [out bf16, softmax_lse]."""
     B, Sq, H, D = q.shape
     Sk, Hk = k.shape[1], k.shape[2]
+    if v.shape[-1] != D:
+        raise RuntimeError(f"fwd_fp8: head dims ({D}, {v.shape[-1]}): the fp8 path has no kernel for a v head dim that differs from q / k")
     if tuple(k.shape) != (B, Sk, Hk, D) or tuple(v.shape) != (B, Sk, Hk, D):
         raise RuntimeError("key/value shape mismatch")
     if H % Hk != 0:
@@ -360,6 +389,8 @@ def varlen_fwd_fp8(q, k, v, out_, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_
     B = cu_seqlens_q.numel() - 1
     if B <= 0 or cu_seqlens_k.numel() != B + 1:
         raise RuntimeError("cu_seqlens_q/k must have shape (batch_size + 1) with batch_size > 0")
+    if v.shape[-1] != D:
+        raise RuntimeError(f"varlen_fwd_fp8: head dims ({D}, {v.shape[-1]}): the fp8 path has no kernel for a v head dim that differs from q / k")
     if tuple(k.shape) != (total_k, Hk, D) or tuple(v.shape) != (total_k, Hk, D):
         raise RuntimeError("key/value shape mismatch")
     if H % Hk != 0:
@@ -465,6 +496,12 @@ def bwd(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, alibi_slopes_, p_dropout
         raise RuntimeError("head_size should be a multiple of 8 and at most 256")
     if H % Hk != 0:
         raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    Dv = v.shape[-1]
+    check_head_dim_pair("bwd", D, Dv, p_dropout=p_dropout, softcap=softcap, alibi_slopes=alibi_slopes_)
+    if Dv != D and (tuple(k.shape) != (B, Sk, Hk, D) or tuple(v.shape) != (B, Sk, Hk, Dv)):
+        raise RuntimeError("key/value shape mismatch")
+    if Dv != D and (tuple(out.shape) != (B, Sq, H, Dv) or tuple(dout.shape) != (B, Sq, H, Dv)):
+        raise RuntimeError(f"out and dout must have shape (batch, seqlen_q, nheads, {Dv}): v's head dim")
     dq, dk, dv = _bwd_out(dq_, q, "dq"), _bwd_out(dk_, k, "dk"), _bwd_out(dv_, v, "dv")
     delta = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     if Sq == 0 or Sk == 0:  # flash_api.cpp:992-999
@@ -481,6 +518,7 @@ def bwd(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, alibi_slopes_, p_dropout
         setattr(a, nm + "_row_stride", t.stride(1))
         setattr(a, nm + "_head_stride", t.stride(2))
     a.b, a.h, a.h_k, a.d = B, H, Hk, D
+    a.d_v = Dv if Dv != D else 0
     a.seqlen_q, a.seqlen_k, a.total_q, a.total_k = Sq, Sk, B * Sq, B * Sk
     rng = _bwd_rng(p_dropout, rng_state, q.device)
     if rng is not None:
@@ -505,6 +543,12 @@ def varlen_bwd(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, cu_seqlens_q, cu_
     B = cu_seqlens_q.numel() - 1
     if D % 8 != 0 or D > 256:
         raise RuntimeError("head_size should be a multiple of 8 and at most 256")
+    Dv = v.shape[-1]
+    check_head_dim_pair("varlen_bwd", D, Dv, p_dropout=p_dropout, softcap=softcap, alibi_slopes=alibi_slopes_)
+    if Dv != D and (tuple(k.shape) != (total_k, Hk, D) or tuple(v.shape) != (total_k, Hk, Dv)):
+        raise RuntimeError("key/value shape mismatch")
+    if Dv != D and (tuple(out.shape) != (total_q, H, Dv) or tuple(dout.shape) != (total_q, H, Dv)):
+        raise RuntimeError(f"out and dout must have shape (total_q, nheads, {Dv}): v's head dim")
     dq, dk, dv = _bwd_out(dq_, q, "dq"), _bwd_out(dk_, k, "dk"), _bwd_out(dv_, v, "dv")
     delta = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
     if zero_tensors:  # flash_api.cpp:1171-1176
@@ -528,6 +572,7 @@ def varlen_bwd(dout, q, k, v, out, softmax_lse, dq_, dk_, dv_, cu_seqlens_q, cu_
     _check_dev(seqused_q, seqused_k)
     a.seqused_q, a.seqused_k = _ptr(seqused_q), _ptr(seqused_k)
     a.b, a.h, a.h_k, a.d = B, H, Hk, D
+    a.d_v = Dv if Dv != D else 0
     a.seqlen_q, a.seqlen_k, a.total_q, a.total_k = int(max_seqlen_q), int(max_seqlen_k), total_q, total_k
     rng = _bwd_rng(p_dropout, rng_state, q.device)
     if rng is not None:
@@ -583,6 +628,8 @@ def fwd_kvcache(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
             raise RuntimeError("rotary_cos/sin must have contiguous last dimension and equal row strides")
     B, Sq, H, D = q.shape
     Hk = kcache.shape[2]
+    if vcache.shape[-1] != D:
+        raise RuntimeError(f"fwd_kvcache: head dims ({D}, {vcache.shape[-1]}): the KV-cache path has no kernel for a v head dim that differs from q / k")
     page = kcache.shape[1] if paged else 0
     Sk = block_table_.shape[1] * page if paged else kcache.shape[1]
     if D > 256:
@@ -706,6 +753,8 @@ def fwd_kvcache_fp8(q, kcache, vcache, k_, v_, seqlens_k_, cache_batch_idx_, blo
         raise RuntimeError("batch size must be positive")
     if H % Hk != 0:
         raise RuntimeError("Number of heads in key/value must divide number of heads in query")
+    if vcache.shape[-1] != D:
+        raise RuntimeError(f"fwd_kvcache_fp8: head dims ({D}, {vcache.shape[-1]}): the fp8 path has no kernel for a v head dim that differs from q / k")
     if kcache.shape[3] != D or tuple(vcache.shape) != tuple(kcache.shape):
         raise RuntimeError("kcache / vcache shape mismatch")
     if paged:

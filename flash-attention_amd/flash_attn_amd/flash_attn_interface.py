@@ -41,6 +41,24 @@ def _pad_head_dim(*ts):
     return tuple(torch.nn.functional.pad(t, [0, pad]) for t in ts)
 
 
+def _check_head_dims(fn, q, v, dropout_p=0.0, softcap=0.0, alibi_slopes=None, return_softmax=False, block_table=None, leftpad_k=None):
+    """v may have a head dim of its own (Dv != D; built: D = 192 with Dv = 128, DeepSeek-V2/V3 multi-head latent attention).  Everything else about
+    such a call is refused here by name, on shapes and flags alone -- before the backend is reached, so also under fake tensors.  Returns True
+    when the head dims differ (then nothing is padded: the one built pair is a multiple of 8 on both sides)."""
+    d, dv = q.shape[-1], v.shape[-1]
+    if d == dv:
+        return False
+    from .backend import check_head_dim_pair
+    check_head_dim_pair(fn, d, dv, p_dropout=dropout_p, softcap=softcap, alibi_slopes=alibi_slopes, return_softmax=return_softmax,
+                        block_table=block_table, leftpad_k=leftpad_k)
+    return True
+
+
+def _refuse_head_dims(fn, d, dv, what):
+    if d != dv:
+        raise RuntimeError(f"{fn}: head dims ({d}, {dv}): {what} has no kernel for a v head dim that differs from q / k")
+
+
 # The four raw wrappers are registered as custom ops (namespace ``flash_attn_amd``) with fake implementations, like the
 # reference's ``flash_attn::_flash_attn_forward`` etc. (reference :84-144, :153-243, :252-338, :347-452), so that
 # torch.compile / export trace through them without graph breaks; the public functions below call the registered ops.
@@ -56,8 +74,9 @@ def _fwd_impl(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, dropout_p: floa
 
 def _fwd_fake(q, k, v, dropout_p, softmax_scale, causal, window_size_left, window_size_right, softcap, alibi_slopes,
               return_softmax):
-    B, Sq, H, _ = q.shape
-    out = torch.empty_like(q)
+    B, Sq, H, D = q.shape
+    # (out has v's head dim; Dv == D keeps the layout of q as before)
+    out = torch.empty_like(q) if v.shape[-1] == D else torch.empty((B, Sq, H, v.shape[-1]), dtype=q.dtype, device=q.device)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
     p = (torch.empty((B, H, Sq, k.shape[1]), dtype=torch.uint8, device=q.device) if return_softmax
          else torch.empty((0,), dtype=q.dtype, device=q.device))
@@ -82,8 +101,8 @@ def _varlen_fwd_impl(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cu_seqle
 def _varlen_fwd_fake(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
                      window_size_left=-1, window_size_right=-1, softcap=0.0, alibi_slopes=None, return_softmax=False,
                      block_table=None, leftpad_k=None, seqused_k=None, zero_tensors=False):
-    total_q, H, _ = q.shape
-    out = torch.empty_like(q)
+    total_q, H, D = q.shape
+    out = torch.empty_like(q) if v.shape[-1] == D else torch.empty((total_q, H, v.shape[-1]), dtype=q.dtype, device=q.device)
     lse = torch.empty((H, total_q), dtype=torch.float32, device=q.device)
     p = (torch.empty((H, total_q, max_seqlen_k), dtype=torch.uint8, device=q.device) if return_softmax
          else torch.empty((0,), dtype=q.dtype, device=q.device))
@@ -225,6 +244,7 @@ def _fp8_route(q, k, v, batch, dropout_p, softmax_scale, softcap, alibi_slopes, 
         raise RuntimeError("q_descale / k_descale / v_descale apply to float8_e4m3fn inputs only")
     if k.dtype != fp8 or v.dtype != fp8:
         raise RuntimeError("query, key and value must have the same dtype")
+    _refuse_head_dims("flash_attn (fp8)", q.shape[-1], v.shape[-1], "the fp8 forward")
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         raise RuntimeError("the fp8 forward has no backward: call it under torch.no_grad() or on tensors that do not require grad")
     if dropout_p != 0.0 or softcap != 0.0 or alibi_slopes is not None:
@@ -316,27 +336,28 @@ class _AttnFn(torch.autograd.Function):
                 return_softmax, is_grad_enabled):
         needs_grad = is_grad_enabled and any(t.requires_grad for t in (q, k, v))
         if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        d_orig = q.shape[-1]
-        q, k, v = _pad_head_dim(q, k, v)
+            softmax_scale = q.shape[-1] ** (-0.5)   # (q's head dim, also when v has its own -- as the reference)
+        d_orig, dv_orig = q.shape[-1], v.shape[-1]
+        if not _check_head_dims("flash_attn_func", q, v, dropout_p, softcap, alibi_slopes, return_softmax and dropout_p > 0):
+            q, k, v = _pad_head_dim(q, k, v)
         out_p, lse, s_dmask, rng_state = _flash_attn_forward(
             q, k, v, dropout_p, softmax_scale, causal, window_size[0], window_size[1], softcap, alibi_slopes,
             return_softmax and dropout_p > 0)
         if needs_grad:
             ctx.save_for_backward(q, k, v, out_p, lse, rng_state)
-            ctx.cfg = (dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig)
-        out = out_p[..., :d_orig]
+            ctx.cfg = (dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig, dv_orig)
+        out = out_p[..., :dv_orig]
         return out if not return_softmax else (out, lse, s_dmask)
 
     @staticmethod
     def backward(ctx, dout, *unused):
         q, k, v, out, lse, rng_state = ctx.saved_tensors
-        dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig = ctx.cfg
+        dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig, dv_orig = ctx.cfg
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         (dout_p,) = _pad_head_dim(dout) if dout.shape[-1] % 8 else (dout,)
         _flash_attn_backward(dout_p, q, k, v, out, lse, dq, dk, dv, dropout_p, softmax_scale, causal, window_size[0],
                              window_size[1], softcap, alibi_slopes, deterministic, rng_state)
-        return (dq[..., :d_orig], dk[..., :d_orig], dv[..., :d_orig]) + (None,) * 9
+        return (dq[..., :d_orig], dk[..., :d_orig], dv[..., :dv_orig]) + (None,) * 9
 
 
 class _VarlenAttnFn(torch.autograd.Function):
@@ -347,28 +368,29 @@ class _VarlenAttnFn(torch.autograd.Function):
                 window_size, softcap, alibi_slopes, deterministic, return_softmax, block_table, is_grad_enabled):
         needs_grad = is_grad_enabled and any(t.requires_grad for t in (q, k, v))
         if softmax_scale is None:
-            softmax_scale = q.shape[-1] ** (-0.5)
-        d_orig = q.shape[-1]
-        q, k, v = _pad_head_dim(q, k, v)
+            softmax_scale = q.shape[-1] ** (-0.5)   # (q's head dim, also when v has its own -- as the reference)
+        d_orig, dv_orig = q.shape[-1], v.shape[-1]
+        if not _check_head_dims("flash_attn_varlen_func", q, v, dropout_p, softcap, alibi_slopes, return_softmax and dropout_p > 0, block_table):
+            q, k, v = _pad_head_dim(q, k, v)
         out_p, lse, s_dmask, rng_state = _flash_attn_varlen_forward(
             q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal,
             window_size[0], window_size[1], softcap, alibi_slopes, return_softmax and dropout_p > 0, block_table)
         if needs_grad:
             ctx.save_for_backward(q, k, v, out_p, lse, cu_seqlens_q, cu_seqlens_k, rng_state)
             ctx.cfg = (max_seqlen_q, max_seqlen_k, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes,
-                       deterministic, d_orig)
-        out = out_p[..., :d_orig]
+                       deterministic, d_orig, dv_orig)
+        out = out_p[..., :dv_orig]
         return out if not return_softmax else (out, lse, s_dmask)
 
     @staticmethod
     def backward(ctx, dout, *unused):
         q, k, v, out, lse, cu_q, cu_k, rng_state = ctx.saved_tensors
-        mq, mk, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig = ctx.cfg
+        mq, mk, dropout_p, softmax_scale, causal, window_size, softcap, alibi_slopes, deterministic, d_orig, dv_orig = ctx.cfg
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
         (dout_p,) = _pad_head_dim(dout) if dout.shape[-1] % 8 else (dout,)
         _flash_attn_varlen_backward(dout_p, q, k, v, out, lse, dq, dk, dv, cu_q, cu_k, mq, mk, dropout_p, softmax_scale,
                                     causal, window_size[0], window_size[1], softcap, alibi_slopes, deterministic, rng_state)
-        return (dq[..., :d_orig], dk[..., :d_orig], dv[..., :d_orig]) + (None,) * 14
+        return (dq[..., :d_orig], dk[..., :d_orig], dv[..., :dv_orig]) + (None,) * 14
 
 
 class _PaddedAttnFn(torch.autograd.Function):
@@ -416,6 +438,7 @@ def flash_attn_padded_func(q, k, v, seqlens_q, seqlens_k=None, starts_q=None, st
     of pad_input(flash_attn_varlen_func(unpad_input(..))) without the three gather / scatter passes and the unpadded copies."""
     B, Sq = q.shape[0], q.shape[1]
     Sk = k.shape[1]
+    _refuse_head_dims("flash_attn_padded_func", q.shape[-1], v.shape[-1], "the padded-batch path")
 
     if B == 0 or Sq == 0 or Sk == 0:   # nothing to attend: the padded output (and, through autograd, the gradients) are zeros
         if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
@@ -447,6 +470,8 @@ def flash_attn_func(q, k, v, dropout_p=0.0, softmax_scale=None, causal=False, wi
     """q (B,Sq,H,D); k, v (B,Sk,Hk,D) with H % Hk == 0 (MQA/GQA).  Causal / window masks are aligned to the
     bottom-right corner; ``window_size=(l, r)`` lets query i see keys [i+Sk-Sq-l, i+Sk-Sq+r].
     Returns out (B,Sq,H,D) (and softmax_lse (B,H,Sq), S_dmask when ``return_attn_probs``).
+    v may have a head dim of its own, (B,Sk,Hk,Dv): D = 192 with Dv = 128 is built (bf16 / fp16, masks, MQA / GQA, forward and backward; out is
+    (B,Sq,H,Dv), the default softmax_scale stays D ** -0.5); dropout (and with it the S_dmask of return_attn_probs), softcap and ALiBi are refused for it.
     float8_e4m3fn q / k / v (FA3's fp8 forward): optional fp32 (B, Hk) ``q_descale`` / ``k_descale`` / ``v_descale``, bf16 out, forward only
     (head dims 64 / 128; ``return_attn_probs`` gives (out, softmax_lse, None))."""
     if q.dtype == torch.float8_e4m3fn or q_descale is not None or k_descale is not None or v_descale is not None:
@@ -527,7 +552,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q, ma
                            deterministic=False, return_attn_probs=False, block_table=None, *, q_descale=None, k_descale=None,
                            v_descale=None):
     """q (total_q,H,D); k, v (total_k,Hk,D); cu_seqlens_* int32 (B+1) cumulative lengths on the device.
-    Returns out (total_q,H,D) (and softmax_lse (H,total_q) when ``return_attn_probs``).  float8_e4m3fn inputs: as flash_attn_func
+    Returns out (total_q,H,D) (and softmax_lse (H,total_q) when ``return_attn_probs``).  v may be (total_k,Hk,Dv) with D = 192, Dv = 128 as in
+    flash_attn_func (no block_table then).  float8_e4m3fn inputs: as flash_attn_func
     (descales (B, Hk) with B = len(cu_seqlens_q) - 1; no block_table)."""
     if q.dtype == torch.float8_e4m3fn or q_descale is not None or k_descale is not None or v_descale is not None:
         scale = _fp8_route(q, k, v, cu_seqlens_q.shape[0] - 1, dropout_p, softmax_scale, softcap, alibi_slopes,
@@ -572,6 +598,7 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     batch entry of q, bf16 out, head dims 64 / 128; new keys / values are appended as bytes (quantise them with the cache's scale); rotary,
     ``cache_leftpad``, ALiBi and softcap are refused."""
     q, k, v = (_unit_stride_last(t) for t in (q, k, v))
+    _refuse_head_dims("flash_attn_with_kvcache", q.shape[-1], v_cache.shape[-1], "the KV-cache path")
     fp8 = (q.dtype == torch.float8_e4m3fn or k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn
            or q_descale is not None or k_descale is not None or v_descale is not None)
     if fp8:

@@ -32,6 +32,10 @@
  *     set, static_switch.h:92-110); a size in between runs the next built size's kernels with a run-time column bound: the 16-byte chunks
  *     behind d are read as zeros and never stored, so q / k / v / out / gradients keep their own row pitch -- no padded copies (the reference
  *     rounds internally the same way, flash_api.cpp:458,872);
+ *   - v may have a head dim of its own (FaFwdParams::d_v): q / k (.., 192), v / o (.., 128) is built (fa_fwd / fa_varlen_fwd: plain attention under
+ *     causal / window masks, MHA / GQA / MQA, seqused_q / seqused_k; softmax_scale is the caller's -- the binders default to d ** -0.5, d = q's head dim).  Any
+ *     other pair with d_v != d, and this pair with dropout, softcap, ALiBi, return_softmax, block_table, leftpad_k, a KV cache or FP8, returns
+ *     FA_ERR_UNSUPPORTED with a message naming both head dims or the argument;
  *   - return value 0 = enqueued; negative = FA_ERR_* (message via fa_last_error()).
  */
 #ifndef FA_GFX950_H_
@@ -87,7 +91,9 @@ typedef struct FaFwdParams {
   int32_t page_block_size;          /* keys per page, multiple of 256 (reference flash_api.cpp:1318)  */
   int32_t num_splits;               /* fa_fwd_kvcache: 0 = heuristic, 1 = no split, >1 = split the keys this many ways */
   float p_dropout;                  /* probability to DROP, in [0, 1); 0 = off                         */
-  int32_t reserved0;
+  int32_t d_v;                      /* head dim of v / o when it differs from d (took the place of a reserved field; 0 = d).  fa_fwd / fa_varlen_fwd only,
+                                       and only the pair d = 192, d_v = 128 (DeepSeek-V2/V3 multi-head latent attention: 128 "nope" + 64 rotary q/k
+                                       channels, 128 v channels; the reference's hopper/flash_api.cpp:782-786): v is (.., Hk, d_v), o (.., H, d_v) */
   /* dropout (p_dropout > 0): */
   const uint64_t* rng_state;        /* device, 2 x u64 {seed, offset} (reference rng_state, flash_api.cpp:496-515) */
   uint8_t* randval;                 /* optional out: the random byte of every (query, key) pair; a pair is KEPT iff
@@ -186,7 +192,8 @@ typedef struct FaBwdParams {
   float softcap;
   int32_t deterministic;        /* accepted; this implementation is always deterministic */
   float p_dropout;              /* as in the forward call                                  */
-  int32_t reserved[3];
+  int32_t d_v;                  /* head dim of v / o / dout / dv when it differs from d (took the first reserved field; 0 = d), as FaFwdParams::d_v */
+  int32_t reserved[2];
   const uint64_t* rng_state;    /* device {seed, offset} the forward used (p_dropout > 0) */
   const int32_t* seqused_q;     /* ABI v6, optional (B): as FaFwdParams::seqused_q; dq rows past it are not written */
   const int32_t* seqused_k;     /* ABI v6, optional (B): keys of entry b in use.  In the backward it can only SHORTEN an entry: the length is
@@ -226,11 +233,11 @@ void fa_knobs_reload(void);
 /* Which kernels the calling thread's last fa_fwd* / fa_bwd* call enqueued (for tests and the benchmark's labels; the
  * reference exposes nothing comparable -- its dispatch is compile-time, flash_fwd_launch_template.h).  Fills up to n of
  * FA_SCHEDULE_FIELDS int32: {forward kernel id (0 none, 1 lock-step fa_fwd_kernel, 2 pipelined fa_fwd_il_kernel,
- * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel, 5 FP8 KV-cache fa_fwd_fp8_kv_kernel), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
+ * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel, 5 FP8 KV-cache fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel: v / o head dim of its own), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
  * varlen work list used, head dim, bf16, dQ-kernel waves, backward work lists used, backward spilled dS (5 contractions),
  * query heads packed into the rows of a block (fa_fwd_kvcache, 1 = none), dK/dV schedule (8 waves x 32 keys, 4 at head dim 256,
- * or 64 = 4 waves x 64 keys)}; returns FA_SCHEDULE_FIELDS (fields are only ever appended). */
-#define FA_SCHEDULE_FIELDS 12
+ * or 64 = 4 waves x 64 keys), head dim of v / o (= head dim unless FaFwdParams::d_v set it)}; returns FA_SCHEDULE_FIELDS (fields are only ever appended). */
+#define FA_SCHEDULE_FIELDS 13
 int fa_last_schedule(int32_t* out, int n);
 /* Name of the forward kernel instantiation of that call, e.g. "fa::fa_fwd_il_kernel<bf16,128,4,3>" ("" if none). */
 const char* fa_last_kernel_name(void);
