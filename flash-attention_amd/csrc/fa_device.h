@@ -110,6 +110,10 @@ FA_DEVINL void lds_dma_16B(const void* gsrc, const char FA_LDS* lds_dst_uniform)
                : "memory");
 }
 FA_DEVINL void lds_dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// at most N of this wave's LDS-DMA instructions still in flight (they retire in order)
+template <int N> FA_DEVINL void dma_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// every LDS write and read of this wave done, then the workgroup barrier -- without the vmcnt(0) a __syncthreads() puts in front of it
+FA_DEVINL void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // XCD-aware work mapping for 1-D grids.  Workgroup `bid` is observed to run on XCD bid % 8 (performance only,
 // never correctness).  Work items are numbered unit * unit_size + item; a *unit* (e.g. all query blocks of the

@@ -96,6 +96,8 @@ __global__ void __launch_bounds__(NW * 64, D > 128 ? 1 : 2) fa_fwd_kernel(const 
   const int hi = lane >> 5, qi = lane & 31;
 
   // ---- which (batch, head, query block) -------------------------------------------------------
+  // (From here to the lane limits this is the geometry fa_fwd_block.h holds for the other 32-rows-per-wave forwards, with every feature bit set;
+  // it stays spelled out because this unit's ~130 instantiations have a pinned spill budget that moves with any reshaping -- keep the two in step.)
   int b, h, m_block, split = 0;
   if (p.work_list) {  // varlen: non-empty blocks only, heaviest first
     if (!work_list_item(p.work_list, blockIdx.x, p.h, p.h_k, b, h, m_block)) return;

@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "fa_device.h"
+#include "fa_fwd_block.h"
 #include "fa_kernel_params.h"
 #include "fa_launch.h"
 
@@ -60,71 +61,29 @@ __global__ void __launch_bounds__(NW * 64, 2) fa_fwd_dv_kernel(const FwdK p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5, qi = lane & 31;
 
-  // ---- which (batch, head, query block): as fa_fwd_kernel --------------------------------------
-  int b, h, m_block;
-  if (p.work_list) {  // varlen: non-empty blocks only, heaviest first
-    if (!work_list_item(p.work_list, blockIdx.x, p.h, p.h_k, b, h, m_block)) return;
-  } else {
-    const int w = xcd_interleave(blockIdx.x, p.n_units, p.unit_size, p.unit_hpx);
-    if (w < 0) return;
-    const int bh = w / p.nmb;
-    const int mbr = w - bh * p.nmb;
-    m_block = (p.wr >= 0) ? (p.nmb - 1 - mbr) : mbr;
-    b = bh / p.h;
-    h = bh - b * p.h;
-  }
-  const int hk = h / p.hk_ratio;
-
-  int sq = p.sq, sk = p.sk;
-  int64_t q_row0 = 0, k_row0 = 0;  // first row of this sequence in the packed tensors
-  int64_t q_boff = (int64_t)b * p.q_bs, k_boff = (int64_t)b * p.k_bs, v_boff = (int64_t)b * p.v_bs, o_boff = (int64_t)b * p.o_bs;
-  if (p.cu_q) {
-    const int c0 = p.cu_q[b];
-    sq = p.cu_q[b + 1] - c0;
-    q_row0 = c0;
-    q_boff = 0;
-    o_boff = 0;
-  }
-  if (p.seqused_q) sq = min(sq, p.seqused_q[b]);
-  if (p.cu_k) {
-    const int c0 = p.cu_k[b];
-    sk = p.cu_k[b + 1] - c0;
-    k_row0 = c0;
-    k_boff = 0;
-    v_boff = 0;
-  }
-  if (p.seqused_k) sk = min(p.seqused_k[b], p.cu_k ? sk : p.sk);  // keys in use, never beyond the entry's slot
-  const int m0 = m_block * BM;
+  // ---- which (batch, head, query block), its sequence, key tiles and visibility limits: fa_fwd_block.h ----
+  constexpr int F = FB_LIST | FB_VARLEN | FB_SEQUSED;  // the host contract: no packing, key splits, cache arguments or leftpad_k
+  FwdWork wk;
+  if (!fwd_work<F>(p, blockIdx.x, wk)) return;
+  const int b = wk.b, h = wk.h, hk = h / p.hk_ratio;
+  const FwdSeq seq = fwd_seq<F>(p, b);
+  const int sq = seq.sq, sk = seq.sk;
+  const int m0 = wk.m_block * BM;
   if (m0 >= sq) return;
 
-  const E* __restrict__ qp = (const E*)p.q + q_boff + q_row0 * p.q_rs + (int64_t)h * p.q_hs;
-  const E* __restrict__ kp = (const E*)p.k + k_boff + k_row0 * p.k_rs + (int64_t)hk * p.k_hs;
-  const E* __restrict__ vp = (const E*)p.v + v_boff + k_row0 * p.v_rs + (int64_t)hk * p.v_hs;
-  E* __restrict__ op = (E*)p.o + o_boff + q_row0 * p.o_rs + (int64_t)h * p.o_hs;
-  float* __restrict__ lsep = p.cu_q ? (p.lse + (int64_t)h * p.total_q + q_row0) : (p.lse + ((int64_t)b * p.h + h) * p.sq);
+  const E* __restrict__ qp = (const E*)p.q + seq.q_off + (int64_t)h * p.q_hs;
+  const E* __restrict__ kp = (const E*)p.k + seq.k_off + (int64_t)hk * p.k_hs;
+  const E* __restrict__ vp = (const E*)p.v + seq.v_off + (int64_t)hk * p.v_hs;
+  E* __restrict__ op = (E*)p.o + seq.o_off + (int64_t)h * p.o_hs;
+  float* __restrict__ lsep = fwd_lse_row<F>(p, seq, b, h);
 
-  // ---- key range of the block, per-wave and per-lane visibility limits --------------------------
   const int shift = sk - sq;  // bottom-right alignment
-  const int blk_last = min(m0 + BM, sq) - 1;
-  int kmax = sk - 1, kmin = 0;
-  if (p.wr >= 0) kmax = min(kmax, blk_last + shift + p.wr);
-  if (p.wl >= 0) kmin = max(0, m0 + shift - p.wl);
-  const int n_min = kmin / BN;
-  const int n_max = (kmax >= kmin) ? (kmax / BN + 1) : n_min;
-  const int n_tiles = n_max - n_min;
-
-  const int w_row0 = m0 + wave * 32;
-  const int w_row1 = min(w_row0 + 31, sq - 1);
-  const bool wave_valid = w_row0 < sq;
-  const int w_kmax = (p.wr >= 0) ? min(sk - 1, w_row1 + shift + p.wr) : sk - 1;     // last key any row sees
-  const int w_kmin = (p.wl >= 0) ? max(0, w_row0 + shift - p.wl) : 0;               // first key any row sees
-  const int w_full_hi = (p.wr >= 0) ? min(sk - 1, w_row0 + shift + p.wr) : sk - 1;  // keys <= this: visible to all rows
-  const int w_full_lo = (p.wl >= 0) ? (w_row1 + shift - p.wl) : 0;                  // keys >= this: visible to all rows
-
-  const int my_row = w_row0 + qi;
-  const bool row_valid = my_row < sq;
-  const int lim_hi = (p.wr >= 0) ? min(sk - 1, my_row + shift + p.wr) : sk - 1;
-  const int lim_lo = (p.wl >= 0) ? (my_row + shift - p.wl) : 0;
+  const TileRange tr = tile_range<F>(p, key_window(m0, min(m0 + BM, sq) - 1, shift, sk, p.wl, p.wr), 0);
+  const int n_min = tr.n_min, n_tiles = tr.n_tiles;
+  const int w_row0 = m0 + wave * 32, my_row = w_row0 + qi;
+  const bool wave_valid = w_row0 < sq, row_valid = my_row < sq;
+  const KeyWindow wv = key_window(w_row0, min(w_row0 + 31, sq - 1), shift, sk, p.wl, p.wr);  // this wave's 32 rows
+  const KeyWindow ln = key_window(my_row, my_row, shift, sk, p.wl, p.wr);                      // this lane's row
   const float cs = p.scale_log2;
   const float thr = p.rescale_thr;
 
@@ -203,7 +162,7 @@ __global__ void __launch_bounds__(NW * 64, 2) fa_fwd_dv_kernel(const FwdK p) {
 
   auto tile_active = [&](int j) __attribute__((always_inline)) {  // j relative to n_min
     const int kv0 = (n_min + j) * BN;
-    return wave_valid && (j < n_tiles) && (kv0 <= w_kmax) && (kv0 + BN - 1 >= w_kmin);
+    return wave_valid && (j < n_tiles) && (kv0 <= wv.any_hi) && (kv0 + BN - 1 >= wv.any_lo);
   };
 
   // S^T[key][query] of the tile in K buffer `buf`: 12 k-steps x 2 key blocks; operand reads run PF k-steps ahead of their MFMAs
@@ -237,10 +196,10 @@ __global__ void __launch_bounds__(NW * 64, 2) fa_fwd_dv_kernel(const FwdK p) {
   // mask + online softmax of s -> pf (P^T as B operand), updates m_run / l_run / o_acc scale (fa_fwd_kernel's rule, plain variant)
   auto softmax_step = [&](int j) __attribute__((always_inline)) {
     const int kv0 = (n_min + j) * BN;
-    const bool need_mask = (kv0 + BN - 1 > w_full_hi) || (kv0 < w_full_lo);
+    const bool need_mask = (kv0 + BN - 1 > wv.all_hi) || (kv0 < wv.all_lo);
     if (need_mask) {
-      const int rel_hi = lim_hi - kv0 - 4 * hi;
-      const int rel_lo = lim_lo - kv0 - 4 * hi;
+      const int rel_hi = ln.all_hi - kv0 - 4 * hi;
+      const int rel_lo = ln.all_lo - kv0 - 4 * hi;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll

@@ -1,7 +1,7 @@
 // Forward attention of FP8 (OCP e4m3) queries against an FP8 KV cache (fa_fwd_kvcache_fp8): the decode-side twin of fa_fwd_fp8.hip.
 //
-// Contract, operand maps, the transposed V image and the numerics are those of fa_fwd_fp8.hip (S = softmax_scale * q_descale * k_descale * q.k^T
-// on the exact fp8 values, P rounded to e4m3, v_descale folded into 1 / l, deferred rescale capped at 8; probe_gfx950.hip checks the lane maps).
+// Contract, operand maps, the transposed V image and the numerics are those of fa_fwd_fp8.hip: both kernels take their tile code from fa_fp8_tile.h,
+// where they are written down, and their block geometry from fa_fwd_block.h.
 // What this kernel adds is the cache addressing and the decode schedule:
 //   - keys in use per batch entry = seqused_k[b] + seqused_add, never more than the addressable capacity; rows past it are never read (a DMA lane
 //     whose row lies behind the last key re-fetches the last key, and its score is masked);
@@ -21,36 +21,15 @@
 #include <cstdio>
 
 #include "fa_device.h"
+#include "fa_fp8_tile.h"
+#include "fa_fwd_block.h"
 #include "fa_kernel_params.h"
 #include "fa_launch.h"
 
 namespace fa {
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-namespace kv8 {
-// D = A.B + C on e4m3 A and B (cbsz = blgp = 0), unit E8M0 block scales (127 = 2^0) on both operands
-FA_DEVINL f32x16 mfma_e4m3(i32x8 a, i32x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 127, 0, 127);
-}
-FA_DEVINL i32x8 join16(u32x4 lo, u32x4 hi) {
-  return __builtin_bit_cast(i32x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-// 16-byte chunk swizzles of the row tiles and of the V image: as fa_fwd_fp8.hip (every 16-lane group of a ds_read_b128 meets each 16-byte slot of
-// a 256-byte bank row once)
-template <int D> FA_DEVINL constexpr int swz_row8(int row) {
-  return D == 128 ? (((row >> 1) & 1) | (((row >> 3) & 1) << 1) | (((row >> 2) & 1) << 2)) : ((row >> 2) & 3);
-}
-FA_DEVINL constexpr int swz_img(int d) { return (d >> 2) & 3; }
-// at most N of this wave's LDS-DMA instructions still in flight (they retire in order)
-template <int N> FA_DEVINL void dma_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// every LDS write and read of this wave done, then the workgroup barrier -- without the vmcnt(0) a __syncthreads() puts in front of it
-FA_DEVINL void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-}  // namespace kv8
-
 template <typename E, int D, int NS>
 __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, const Fp8K f8) {
-  using namespace kv8;
   constexpr int NW = 4, BM = NW * 32, BN = 64;
   constexpr int ROW = D;                  // bytes per K / V / Q row
   constexpr int TILE = BN * ROW;          // bytes per K / V tile and per V image
@@ -72,36 +51,25 @@ __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5, qi = lane & 31;
 
-  // ---- which (batch, head, query block, key split): as fa_fwd_kernel ----
-  const int w = xcd_interleave(blockIdx.x, p.n_units, p.unit_size, p.unit_hpx);
-  if (w < 0) return;
-  const int nmbs = p.nmb * p.n_splits;  // key splits of one query block are adjacent work items
-  const int bh = w / nmbs;
-  int mbr = w - bh * nmbs;
-  const int split = __builtin_amdgcn_readfirstlane(mbr % p.n_splits);
-  mbr /= p.n_splits;
-  const int m_block = __builtin_amdgcn_readfirstlane((p.wr >= 0) ? (p.nmb - 1 - mbr) : mbr);
-  const int b = __builtin_amdgcn_readfirstlane(bh / p.h);  // (the divisions run on the vector unit: back to scalar registers, so that the page table is read with scalar loads)
-  const int h = __builtin_amdgcn_readfirstlane(bh) - b * p.h;
-  const int hk = h / p.hk_ratio;
-
-  const int sq = p.sq;
-  int sk = p.sk;
-  if (p.seqused_k) sk = max(0, min(p.seqused_k[b] + p.seqused_add, p.sk));  // keys in use, never beyond the addressable capacity
-  const int bkv = p.kv_batch_idx ? p.kv_batch_idx[b] : b;  // cache row of this batch entry
-  const int64_t k_boff = p.block_table ? 0 : (int64_t)bkv * p.k_bs, v_boff = p.block_table ? 0 : (int64_t)bkv * p.v_bs;  // paged: the page supplies it
-  const int m0 = m_block * BM;
+  // the host contract: no varlen, no work list, no seqused_q, no leftpad_k
+  constexpr int F = FB_CACHE | FB_SPLIT | FB_SCALAR;
+  FwdWork wk;
+  if (!fwd_work<F>(p, blockIdx.x, wk)) return;
+  const int b = wk.b, h = wk.h, split = wk.split, hk = h / p.hk_ratio;
+  const FwdSeq seq = fwd_seq<F>(p, b);
+  const int sq = seq.sq, sk = seq.sk;  // sk: keys in use of this entry's cache row
+  const int m0 = wk.m_block * BM;
   if (m0 >= sq) return;
 
   const int g = p.pack_g;
   const bool packed = g > 1;
   auto q_of = [&](int row) __attribute__((always_inline)) { return packed ? row / g : row; };
 
-  const char* __restrict__ qp = (const char*)p.q + (int64_t)b * p.q_bs + (int64_t)h * g * p.q_hs;
-  const char* __restrict__ kp = (const char*)p.k + k_boff + (int64_t)hk * p.k_hs;
-  const char* __restrict__ vp = (const char*)p.v + v_boff + (int64_t)hk * p.v_hs;
-  __bf16* __restrict__ op = (__bf16*)p.o + (int64_t)b * p.o_bs + (int64_t)h * g * p.o_hs;
-  float* __restrict__ lsep = p.lse + ((int64_t)b * p.h + h) * p.sq;  // packed: (b, h * g + r % g, r / g) == this base + (r % g) * (sq / g) + r / g
+  const char* __restrict__ qp = (const char*)p.q + seq.q_off + (int64_t)h * g * p.q_hs;
+  const char* __restrict__ kp = (const char*)p.k + seq.k_off + (int64_t)hk * p.k_hs;
+  const char* __restrict__ vp = (const char*)p.v + seq.v_off + (int64_t)hk * p.v_hs;
+  __bf16* __restrict__ op = (__bf16*)p.o + seq.o_off + (int64_t)h * g * p.o_hs;
+  float* __restrict__ lsep = fwd_lse_row<F>(p, seq, b, h);  // packed: (b, h * g + r % g, r / g) == this base + (r % g) * (sq / g) + r / g
 
   // descales: per (batch entry of q, kv head) -- not per cache row
   const float qd = f8.q_descale ? f8.q_descale[(int64_t)b * f8.q_bs + (int64_t)hk * f8.q_hs] : 1.f;
@@ -110,36 +78,17 @@ __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, con
   const float cs = p.scale_log2 * qd * kd;  // log2 units per unit of the raw fp8 dot product
   const float thr = p.rescale_thr;
 
-  // ---- key range of the block and of this split, per-wave and per-lane visibility limits ----
+  // ---- key tiles of the block and of this split, visibility limits of this wave's 32 rows and of this lane's row ----
   const int sq_true = packed ? sq / g : sq;
   const int shift = sk - sq_true;  // bottom-right alignment to this entry's own length
-  const int blk_last = min(m0 + BM, sq) - 1;
-  int kmax = sk - 1, kmin = 0;
-  if (p.wr >= 0) kmax = min(kmax, q_of(blk_last) + shift + p.wr);
-  if (p.wl >= 0) kmin = max(0, q_of(m0) + shift - p.wl);
-  int n_min = kmin / BN;
-  int n_max = (kmax >= kmin) ? (kmax / BN + 1) : n_min;
-  if (p.n_splits > 1) {  // this workgroup's share of the key tiles (may be empty)
-    n_min = max(n_min, split * p.split_tiles);
-    n_max = max(n_min, min(n_max, (split + 1) * p.split_tiles));
-  }
-  const int n_tiles = n_max - n_min;
-  const int key_base = n_min * BN;
-
-  const int w_row0 = m0 + wave * 32;
-  const int w_row1 = min(w_row0 + 31, sq - 1);
-  const bool wave_valid = w_row0 < sq;
-  const int w_q0 = q_of(w_row0), w_q1 = q_of(w_row1);
-  const int w_kmax = (p.wr >= 0) ? min(sk - 1, w_q1 + shift + p.wr) : sk - 1;
-  const int w_kmin = (p.wl >= 0) ? max(0, w_q0 + shift - p.wl) : 0;
-  const int w_full_hi = (p.wr >= 0) ? min(sk - 1, w_q0 + shift + p.wr) : sk - 1;
-  const int w_full_lo = (p.wl >= 0) ? (w_q1 + shift - p.wl) : 0;
-  const int my_row = w_row0 + qi;
-  const bool row_valid = my_row < sq;
+  const TileRange tr = tile_range<F>(p, key_window(q_of(m0), q_of(min(m0 + BM, sq) - 1), shift, sk, p.wl, p.wr), split);
+  const int n_min = tr.n_min, n_tiles = tr.n_tiles, key_base = n_min * BN;
+  const int w_row0 = m0 + wave * 32, my_row = w_row0 + qi;
+  const bool wave_valid = w_row0 < sq, row_valid = my_row < sq;
   const int my_q = q_of(my_row);
   const int my_hh = my_row - my_q * g;  // head within the group (0 unless packed)
-  const int lim_hi = (p.wr >= 0) ? min(sk - 1, my_q + shift + p.wr) : sk - 1;
-  const int lim_lo = (p.wl >= 0) ? (my_q + shift - p.wl) : 0;
+  const KeyWindow wv = key_window(q_of(w_row0), q_of(min(w_row0 + 31, sq - 1)), shift, sk, p.wl, p.wr);
+  const KeyWindow ln = key_window(my_q, my_q, shift, sk, p.wl, p.wr);
 
   // ---- K / V tiles global -> LDS by DMA (1 KiB per wave instruction, lane-linear destination; the swizzle is applied to the per-lane source
   // chunk).  Rows past the last key are clamped to the last key: bytes behind an entry's length are never read.
@@ -205,50 +154,8 @@ __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, con
   lds_dma_wait_all();
   lds_barrier();
   i32x8 qreg[KS];
-  {
-    const int row = wave * 32 + qi;
-    const char FA_LDS* rb = lds + I_OFF + row * ROW;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 4 * ks + 2 * hi;
-      qreg[ks] = join16(*(const u32x4 FA_LDS*)(rb + ((c ^ swz_row8<D>(row)) << 4)), *(const u32x4 FA_LDS*)(rb + (((c + 1) ^ swz_row8<D>(row)) << 4)));
-    }
-  }
+  fp8_read_q<D>(qreg, lds + I_OFF, wave * 32 + qi, hi);
   lds_barrier();  // the image buffers are written from the first iteration on
-
-  // ---- V tile -> V^T image (fa_fwd_fp8.hip): thread (kg, dg) moves keys 4 kg .. 4 kg + 3 x head-dim columns 8 dg .. 8 dg + 7
-  constexpr int T_UNITS = 16 * (D / 8);
-  const int t_kg = tid & 15, t_dg = tid >> 4;
-  const int t_key0 = 4 * t_kg;
-  const int t_chunk = 2 * (t_kg & 1) + (t_kg >> 3);  // logical 16-byte chunk of the image row that holds these 4 keys
-  const int t_inoff = 4 * ((t_kg >> 1) & 3);         // byte offset inside that chunk
-  auto transpose_v = [&](int slot, int img) __attribute__((always_inline)) {
-    if (T_UNITS < NW * 64 && tid >= T_UNITS) return;
-    const char FA_LDS* src = lds + V_OFF + slot * TILE;
-    char FA_LDS* dst = lds + I_OFF + img * TILE;
-    u32x2 r[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int row = t_key0 + t;
-      const int lc = t_dg >> 1;  // logical 16-byte chunk of the 8 columns
-      r[t] = *(const u32x2 FA_LDS*)(src + row * ROW + ((lc ^ swz_row8<D>(row)) << 4) + (t_dg & 1) * 8);
-    }
-#pragma unroll
-    for (int ww = 0; ww < 2; ++ww) {  // columns 8 dg + 4 ww .. + 3
-      const unsigned a = r[0][ww], bb = r[1][ww], c = r[2][ww], dd = r[3][ww];
-      const unsigned t0 = __builtin_amdgcn_perm(bb, a, 0x05010400u);
-      const unsigned t1 = __builtin_amdgcn_perm(bb, a, 0x07030602u);
-      const unsigned t2 = __builtin_amdgcn_perm(dd, c, 0x05010400u);
-      const unsigned t3 = __builtin_amdgcn_perm(dd, c, 0x07030602u);
-      const unsigned o[4] = {__builtin_amdgcn_perm(t2, t0, 0x05040100u), __builtin_amdgcn_perm(t2, t0, 0x07060302u),
-                             __builtin_amdgcn_perm(t3, t1, 0x05040100u), __builtin_amdgcn_perm(t3, t1, 0x07060302u)};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int d = 8 * t_dg + 4 * ww + e;
-        *(unsigned FA_LDS*)(dst + d * 64 + ((t_chunk ^ swz_img(d)) << 4) + t_inoff) = o[e];
-      }
-    }
-  };
 
   f32x16 o_acc[DB];
 #pragma unroll
@@ -259,92 +166,23 @@ __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, con
   i32x8 pf = {0, 0, 0, 0, 0, 0, 0, 0};  // packed P^T of the previous tile (B operand)
   bool have_prev = false;
 
-  // O^T += V^T.P^T from image `img`
-  auto pv = [&](int img) __attribute__((always_inline)) {
-    const char FA_LDS* im = lds + I_OFF + img * TILE;
-#pragma unroll
-    for (int db = 0; db < DB; ++db) {
-      const int d = 32 * db + qi;
-      const char FA_LDS* rb = im + d * 64;
-      const i32x8 vt = join16(*(const u32x4 FA_LDS*)(rb + (((2 * hi) ^ swz_img(d)) << 4)), *(const u32x4 FA_LDS*)(rb + (((2 * hi + 1) ^ swz_img(d)) << 4)));
-      o_acc[db] = mfma_e4m3(vt, pf, o_acc[db]);
-    }
-  };
-  // S^T of one 32-key half of the K tile in `slot`
-  auto qk_half = [&](f32x16& s, int slot, int half) __attribute__((always_inline)) {
-    const int row = 32 * half + qi;
-    const char FA_LDS* rb = lds + K_OFF + slot * TILE + row * ROW;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int c = 4 * ks + 2 * hi;
-      const i32x8 kf = join16(*(const u32x4 FA_LDS*)(rb + ((c ^ swz_row8<D>(row)) << 4)), *(const u32x4 FA_LDS*)(rb + (((c + 1) ^ swz_row8<D>(row)) << 4)));
-      s = mfma_e4m3(kf, qreg[ks], s);
-    }
-  };
-  auto apply_mask = [&](f32x16& s, int k0) __attribute__((always_inline)) {
-    const int rel_hi = lim_hi - k0 - 4 * hi;
-    const int rel_lo = lim_lo - k0 - 4 * hi;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int off = acc_row(r, 0);
-      s[r] = ((off <= rel_hi) && (off >= rel_lo)) ? s[r] : -INFINITY;
-    }
-  };
-  // registers 4g .. 4g+3 -> bytes 0 .. 3 of dword base + g
-  auto pack = [&](const f32x16& s, int base) __attribute__((always_inline)) {
-#pragma unroll
-    for (int gg = 0; gg < 4; ++gg) {
-      int ww = __builtin_amdgcn_cvt_pk_fp8_f32(s[4 * gg], s[4 * gg + 1], 0, false);
-      ww = __builtin_amdgcn_cvt_pk_fp8_f32(s[4 * gg + 2], s[4 * gg + 3], ww, true);
-      pf[base + gg] = ww;
-    }
-  };
-
   int slot = 0, slot_pre = PD % NS;  // ring slots of tile u and of tile u + PD
   for (int u = 0; u < n_tiles; ++u) {
     const int img = u & 1;
     if (u + PD < n_tiles) dma_tile(slot_pre, u + PD);
-    transpose_v(slot, img);
-    if (have_prev) pv(img ^ 1);
+    fp8_transpose_v<D, NW * 64>(lds + V_OFF + slot * TILE, lds + I_OFF + img * TILE, tid);
+    if (have_prev) fp8_pv<D>(o_acc, lds + I_OFF + (img ^ 1) * TILE, pf, qi, hi);
     const int k0 = key_base + u * BN;
-    const bool active = wave_valid && k0 <= w_kmax && k0 + BN - 1 >= w_kmin;
+    const bool active = wave_valid && k0 <= wv.any_hi && k0 + BN - 1 >= wv.any_lo;
     if (active) {
       f32x16 sa, sb;
-      qk_half(sa, slot, 0);
-      qk_half(sb, slot, 1);
-      if ((k0 + BN - 1 > w_full_hi) || (k0 < w_full_lo)) {
-        apply_mask(sa, k0);
-        apply_mask(sb, k0 + 32);
+      fp8_qk_half<D>(sa, lds + K_OFF + slot * TILE, qreg, 0, qi, hi);
+      fp8_qk_half<D>(sb, lds + K_OFF + slot * TILE, qreg, 1, qi, hi);
+      if ((k0 + BN - 1 > wv.all_hi) || (k0 < wv.all_lo)) {
+        fp8_mask(sa, ln.all_hi, ln.all_lo, k0, hi);
+        fp8_mask(sb, ln.all_hi, ln.all_lo, k0 + 32, hi);
       }
-      float tmax = fmaxf(sa[0], sb[0]);
-#pragma unroll
-      for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, fmaxf(sa[r], sb[r]));
-      tmax = half_max(tmax);
-      const float m_new = fmaxf(m_run, tmax);
-      const bool grow = (m_new - m_run) * cs > thr;
-      if (__any(grow)) {
-        const float alpha = grow ? fast_exp2((m_run - m_new) * cs) : 1.f;
-        if (grow) m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int db = 0; db < DB; ++db)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
-      }
-      const float neg_mc = (m_run == -INFINITY) ? 0.f : -m_run * cs;
-      float ps0 = 0.f, ps1 = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sa[r] = fast_exp2(__builtin_fmaf(sa[r], cs, neg_mc));
-        sb[r] = fast_exp2(__builtin_fmaf(sb[r], cs, neg_mc));
-        ps0 += sa[r];
-        ps1 += sb[r];
-      }
-      l_run += ps0 + ps1;
-      pack(sa, 0);
-      pack(sb, 4);
+      fp8_softmax_tile<DB>(sa, sb, m_run, l_run, o_acc, pf, cs, thr);
     }
     have_prev = active;
     // this wave's pieces of tile u + 1 have landed; later tiles stay in flight (the DMA retires in order)
@@ -356,7 +194,7 @@ __global__ void __launch_bounds__(256, 2) fa_fwd_fp8_kv_kernel(const FwdK p, con
     slot = (slot + 1 == NS) ? 0 : slot + 1;
     slot_pre = (slot_pre + 1 == NS) ? 0 : slot_pre + 1;
   }
-  if (have_prev) pv((n_tiles - 1) & 1);
+  if (have_prev) fp8_pv<D>(o_acc, lds + I_OFF + ((n_tiles - 1) & 1) * TILE, pf, qi, hi);
   lds_barrier();  // every wave is done with the ring and the images before the epilogue stages O over them
 
   if (!wave_valid) return;

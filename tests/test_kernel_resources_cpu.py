@@ -54,6 +54,12 @@ def test_no_scratch_in_the_hot_kernels():
         for n, v in fam(s).items():
             assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0, (n, v)
     assert sum("fa_fwd_w64_kernel" in n and template_ints(n)[-1] == 2 for n in ks) == 4   # causal-ALiBi variants: bf16 / fp16 x D = 64 / 128
+    # the FP8 forwards (D = 64 / 128; the KV-cache one x ring depths 2, 3, 4) and the d_v forward (bf16 / fp16): the fp16 d_v kernel sits at the 256-register
+    # limit of its launch bounds, and a reload in the FP8 KV-cache kernel's loop would drain its DMA ring
+    for s, count in (("fa_fwd_fp8_kernel", 2), ("fa_fwd_fp8_kv_kernel", 6), ("fa_fwd_dv_kernel", 2)):
+        assert len(fam(s)) == count, (s, sorted(fam(s)))
+        for n, v in fam(s).items():
+            assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0, (n, v)
     # the lock-step forward and the two backward kernels: <E, D, DV, [NW,] FEAT, ...>
     checked = 0
     for s, feat_at in (("fa_fwd_kernel", 3), ("fa_bwd_dkdv_kernel", 2), ("fa_bwd_dq_kernel", 3)):
