@@ -129,14 +129,35 @@ template <typename K> void fill_dropout(K& k, float p_dropout, const uint64_t* r
 // flash_api.cpp:429-437 -- FA3 generalises it as PackGQA, hopper/pack_gqa.h): when all g query heads of a KV group times the
 // query rows fit one 128-row block, the group's heads become rows of that block and K/V are streamed once per KV head instead
 // of once per query head.  Returns g (1 = no packing).
+// The absorbed MLA decode pair (fa_fwd_mla.hip): q / k head dim 576, v / o head dim 512.  Its kernel ALWAYS runs the packed-row layout, in as many 64-row
+// blocks as g * seqlen_q needs (unpacked, 128 heads would stream the cache 128 times).
+inline bool mla_pair(int d, int d_v) { return d == 576 && d_v == 512; }
+constexpr int kMlaBlockRows = 64;
 int pack_group(const FaFwdParams* a) {
   const int g = a->h_k > 0 ? a->h / a->h_k : 1;
+  if (mla_pair(a->d, a->d_v)) return g > 1 ? g : 1;
   if (g <= 1 || !fa::knobs().pack_gqa || (a->d_v > 0 && a->d_v != a->d) || a->cu_seqlens_q || a->seqused_q || a->p_dropout > 0.f || a->seqlen_q < 1 || (long)a->seqlen_q * g > 128) return 1;
   return g;
 }
 int choose_splits(const FaFwdParams* a, int& split_tiles) {
   const int tiles = (a->seqlen_k + 63) / 64;
   split_tiles = tiles;
+  if (mla_pair(a->d, a->d_v)) {
+    // keys are split while the packed rows of a KV head fit the 128 rows every other kernel's rule allows (one or two 64-row blocks); one workgroup per CU:
+    // the fewest splits that give each of the 256 CUs a workgroup, at least 4 tiles per split.  (A choice by arithmetic, not a measurement.)
+    const long rows = (long)a->seqlen_q * pack_group(a);
+    if (rows > 128 || rows < 1 || tiles < 2 || a->num_splits == 1) return 1;
+    int want = a->num_splits;
+    if (want <= 0) {
+      const long units = (long)a->b * a->h_k * ((rows + kMlaBlockRows - 1) / kMlaBlockRows);
+      if (units >= 192) return 1;
+      want = (int)((256 + units - 1) / units);
+      want = std::min(want, std::max(1, tiles / 4));
+    }
+    want = std::max(1, std::min(std::min(want, 64), tiles));   // (64: fa_splitkv_combine_kernel reads one split per lane -- B = 1, H = 128 gets 2 x 64 = 128 workgroups, half the CUs)
+    split_tiles = (tiles + want - 1) / want;
+    return (tiles + split_tiles - 1) / split_tiles;
+  }
   if (a->seqlen_q > 128 || tiles < 2 || a->num_splits == 1) return 1;
   int want = a->num_splits;
   if (want <= 0) {
@@ -151,7 +172,8 @@ int choose_splits(const FaFwdParams* a, int& split_tiles) {
 }
 int64_t splitkv_bytes(const FaFwdParams* a, int n_splits) {
   if (n_splits <= 1) return 0;
-  return (int64_t)n_splits * a->b * a->h * a->seqlen_q * (head_dim_pitch(a->d) + 1) * (int64_t)sizeof(float);
+  const int pitch = mla_pair(a->d, a->d_v) ? 512 : head_dim_pitch(a->d);   // partial rows have the VALUE width
+  return (int64_t)n_splits * a->b * a->h * a->seqlen_q * (pitch + 1) * (int64_t)sizeof(float);
 }
 
 // Forward schedule code: 64 = 64-rows-per-wave kernel (fa_fwd_w64.hip, 4 waves, 256-row blocks), 34 / 38 = software-pipelined
@@ -249,11 +271,11 @@ int fwd_work_list(const FaFwdParams* a, int bm, int min_dense, int wl, int wr, v
   return FA_OK;
 }
 
-int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool forward = false) {
+int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool forward = false, int d_v = 0) {
   if (b <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "batch size must be positive");
   if (h <= 0 || h_k <= 0 || h % h_k != 0)
     return fail(FA_ERR_INVALID_ARGUMENT, "Number of heads in key/value must divide number of heads in query");
-  if (d <= 0 || d > 256 || d % 8 != 0)
+  if (d <= 0 || (d > 256 && !mla_pair(d, d_v)) || d % 8 != 0)   // (576 only together with d_v = 512: check_value_dim says where that pair runs)
     return fail(FA_ERR_INVALID_ARGUMENT, "head dimension must be a multiple of 8 and at most 256");
   if (dtype != FA_DTYPE_FP16 && dtype != FA_DTYPE_BF16)
     return fail(FA_ERR_INVALID_ARGUMENT, "FlashAttention only supports fp16 and bf16 data type");
@@ -266,10 +288,20 @@ int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool fo
 // device, with a message that names both head dims or the argument.
 inline int value_dim(int d, int d_v) { return d_v > 0 ? d_v : d; }
 int check_value_dim(const char* fn, int d, int d_v, float p_dropout, float softcap, const void* alibi, const void* randval, const void* block_table,
-                    const void* leftpad_k, bool kvcache, bool fp8) {
+                    const void* leftpad_k, bool kvcache, bool fp8, bool kvcache_entry = false) {
   if (d_v < 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: d_v must be non-negative (0 = the head dim of q / k), got %d", fn, d_v);
   if (d_v == 0 || d_v == d) return FA_OK;
   if (fp8) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the fp8 path has no kernel for a v head dim that differs from q / k", fn, d, d_v);
+  if (mla_pair(d, d_v)) {   // the absorbed MLA decode shape: fa_fwd_kvcache alone (fa_fwd_mla.hip), plain attention under causal / window masks
+    if (!kvcache_entry)
+      return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the absorbed MLA decode pair is built for fa_fwd_kvcache only (no fa_fwd / fa_varlen_fwd, no backward)", fn, d, d_v);
+    if (p_dropout > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support dropout (p_dropout)", fn, d, d_v);
+    if (softcap > 0.f) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support softcap", fn, d, d_v);
+    if (alibi) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support ALiBi (alibi_slopes)", fn, d, d_v);
+    if (randval) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support return_softmax", fn, d, d_v);
+    if (leftpad_k) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d) do not support leftpad_k (cache_leftpad)", fn, d, d_v);
+    return FA_OK;
+  }
   if (kvcache) return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the KV-cache path has no kernel for a v head dim that differs from q / k", fn, d, d_v);
   if (d != 192 || d_v != 128)
     return fail(FA_ERR_UNSUPPORTED, "%s: head dims (%d, %d): the only built pair with a v head dim that differs from q / k is (192, 128)", fn, d, d_v);
@@ -309,10 +341,24 @@ int resolve_fwd_features(const FaFwdParams* a, int nw, int wr, int n_splits, int
 int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
-  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true)) return rc;
+  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true, a->d_v)) return rc;
   if (int rc = check_value_dim(kvcache ? "fa_fwd_kvcache" : varlen ? "fa_varlen_fwd" : "fa_fwd", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, a->randval,
-                               a->block_table, a->leftpad_k, kvcache || a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;
+                               a->block_table, a->leftpad_k, kvcache || a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false, kvcache)) return rc;
   const bool own_dv = own_value_dim(a->d, a->d_v);
+  const bool mla = kvcache && mla_pair(a->d, a->d_v);
+  if (mla) {
+    // V is the latent part of the same memory: the kernel reads every cache row once and uses it for both products (FwdK::v is never dereferenced)
+    if (a->v != a->k || a->v_batch_stride != a->k_batch_stride || a->v_row_stride != a->k_row_stride || a->v_head_stride != a->k_head_stride)
+      return fail(FA_ERR_UNSUPPORTED, "fa_fwd_kvcache: head dims (576, 512): V must be the first 512 channels of K (v == k with equal batch / row / head strides, "
+                                      "i.e. the view k_cache[..., :512]); a separate V tensor is not supported");
+    if (a->cu_seqlens_q || a->cu_seqlens_k || a->seqused_q)
+      return fail(FA_ERR_UNSUPPORTED, "fa_fwd_kvcache: head dims (576, 512) do not support cu_seqlens_q / cu_seqlens_k / seqused_q");
+    if (a->k_row_stride < 576 || a->q_row_stride % 8 || a->q_head_stride % 8 || a->q_batch_stride % 8 || a->k_row_stride % 8 || a->k_head_stride % 8 || a->k_batch_stride % 8 ||
+        a->o_row_stride % 8 || a->o_head_stride % 8 || a->o_batch_stride % 8)
+      return fail(FA_ERR_INVALID_ARGUMENT, "fa_fwd_kvcache: head dims (576, 512): q / k / o strides must be multiples of 8 elements and the k row stride at least 576");
+    if ((((uintptr_t)a->q | (uintptr_t)a->k) & 15u) != 0 || ((uintptr_t)a->o & 7u) != 0)
+      return fail(FA_ERR_INVALID_ARGUMENT, "fa_fwd_kvcache: head dims (576, 512): q and k must be 16-byte aligned, o 8-byte aligned");
+  }
   if (!a->q || !a->k || !a->v || !a->o || !a->softmax_lse)
     return fail(FA_ERR_INVALID_ARGUMENT, "q, k, v, o and softmax_lse must be non-NULL");
   if (varlen != (a->cu_seqlens_q != nullptr) || varlen != (a->cu_seqlens_k != nullptr))
@@ -378,6 +424,29 @@ int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false
   const bool bounded = dk != a->d;
   if (bounded) k.d_chunks = a->d / 8;
   if (dk > 128 || head_dim_trimmed(dk) || bounded) nw = 4;  // head dim 256: one 4-wave lock-step workgroup per CU (512-register budget); trimmed / bounded dims: 4-wave lock-step
+  if (mla) {  // q / k 576, v / o 512 = the latent part of k: fa_fwd_mla_kernel, always packed rows, 64-row blocks, split keys
+    k.pack_g = pack; k.h = a->h_k; k.hk_ratio = 1; k.sq = a->seqlen_q * pack;
+    k.nmb = (k.sq + kMlaBlockRows - 1) / kMlaBlockRows;
+    int split_tiles = 0;
+    const int ns = choose_splits(a, split_tiles);
+    if (ns > 1) {
+      const int64_t need = splitkv_bytes(a, ns);
+      if (a->workspace && a->workspace_bytes >= need) {
+        k.n_splits = ns; k.split_tiles = split_tiles;
+        k.o_accum = (float*)a->workspace;
+        k.lse_accum = k.o_accum + (int64_t)ns * a->b * a->h * a->seqlen_q * 512;
+      } else if (a->num_splits > 1) {
+        return fail(FA_ERR_WORKSPACE, "fa_fwd_kvcache: num_splits = %d needs a workspace of %lld bytes (fa_fwd_workspace_bytes)", a->num_splits, (long long)need);
+      }  // auto schedule without a workspace: run unsplit
+    }
+    fa::choose_units(a->b, a->h_k, 1, k.nmb * k.n_splits, k.n_units, k.unit_size, k.unit_hpx);
+    int rc = fa::launch_fwd_mla(k, a->dtype == FA_DTYPE_BF16, a->d, a->d_v, (hipStream_t)stream);
+    if (rc == 0 && k.n_splits > 1) rc = fa::launch_splitkv_combine(k, a->dtype == FA_DTYPE_BF16, 512, (hipStream_t)stream);
+    if (rc == -2) return fail(FA_ERR_UNSUPPORTED, "no forward kernel for head dims (%d, %d)", a->d, a->d_v);
+    if (rc == -3) return fail(FA_ERR_UNSUPPORTED, "k row stride too large: one 64-key tile (64 * row_stride * 2 bytes) must span less than 2 GiB");
+    if (rc != 0) return fail(FA_ERR_LAUNCH, "forward kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return FA_OK;
+  }
   if (own_dv) {  // q / k 192, v / o 128: fa_fwd_dv_kernel, 4 waves x 32 rows (no key splits, no packing: refused above / pack_group)
     constexpr int bm = 128;
     k.nmb = (k.sq + bm - 1) / bm;
@@ -499,7 +568,7 @@ int bwd_dkdv_schedule(const FaBwdParams* a) {
 int fill_bwd(const FaBwdParams* a, bool varlen, fa::BwdK& k) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
-  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap)) return rc;
+  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, false, a->d_v)) return rc;
   if (int rc = check_value_dim(varlen ? "fa_varlen_bwd" : "fa_bwd", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, nullptr, nullptr, nullptr, false, false)) return rc;
   if (!a->dout || !a->q || !a->k || !a->v || !a->o || !a->softmax_lse || !a->dq || !a->dk || !a->dv || !a->softmax_d)
     return fail(FA_ERR_INVALID_ARGUMENT, "dout, q, k, v, o, softmax_lse, dq, dk, dv and softmax_d must be non-NULL");
@@ -1042,9 +1111,9 @@ const char* fa_last_kernel_name(void) { return fa::last_schedule().name; }
 // (the schedule resolution of do_fwd for the entry points without a KV cache: same heuristic, same feature resolution, no split keys)
 int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
-  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true)) return rc;
+  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true, a->d_v)) return rc;
   if (int rc = check_value_dim("fa_fwd_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, a->randval, a->block_table, a->leftpad_k,
-                               a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;
+                               a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;   // (the MLA decode pair too: fa_fwd_kvcache only)
   if (own_value_dim(a->d, a->d_v)) return 4;   // fa_fwd_dv_kernel: 4 waves x 32 rows
   int causal = a->is_causal, wl = a->window_left, wr = a->window_right;
   normalize_window(a->seqlen_q, a->seqlen_k, a->alibi_slopes != nullptr, causal, wl, wr);
@@ -1059,7 +1128,7 @@ int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
 }
 int fa_bwd_dq_schedule_query(const FaBwdParams* a) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
-  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap)) return rc;
+  if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, false, a->d_v)) return rc;
   if (int rc = check_value_dim("fa_bwd_dq_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, nullptr, nullptr, nullptr, false, false)) return rc;
   return bwd_dq_schedule(a);
 }
@@ -1111,6 +1180,9 @@ int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
   k.seqlens_k = a->seqlens_k; k.kv_batch_idx = a->cache_batch_idx; k.block_table = a->block_table;
   k.block_table_bs = a->block_table_batch_stride; k.page_size = a->page_block_size;
   k.b = a->b; k.s_new = a->seqlen_new; k.h_k = a->h_k; k.d = a->d;
+  // V is a view of the K rows on both sides (e.g. the absorbed MLA cache: v = k[..., :512]; any dtype, any d): the key copy already writes every byte, once
+  if (a->vnew == a->knew && a->vcache == a->kcache && k.vn_bs == k.kn_bs && k.vn_rs == k.kn_rs && k.vn_hs == k.kn_hs && k.vc_bs == k.kc_bs && k.vc_rs == k.kc_rs && k.vc_hs == k.kc_hs)
+    k.vnew = nullptr;
   if (fp8) {   // bytes -> 16-bit words (a byte copy: nothing is requantised)
     k.d /= 2;
     for (int64_t* st : {&k.kn_bs, &k.kn_rs, &k.kn_hs, &k.vn_bs, &k.vn_rs, &k.vn_hs, &k.kc_bs, &k.kc_rs, &k.kc_hs, &k.vc_bs, &k.vc_rs, &k.vc_hs}) *st /= 2;

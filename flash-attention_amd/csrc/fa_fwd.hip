@@ -634,6 +634,7 @@ __global__ void __launch_bounds__(256) fa_splitkv_combine_kernel(const FwdK p) {
 template <typename E>
 static int launch_combine_e(const FwdK& p, int d, dim3 grid, dim3 block, hipStream_t stream) {
   switch (d) {
+    case 512: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 512, 512>), grid, block, 0, stream, p); break;   // fa_fwd_mla_kernel's partials (value width)
     case 256: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 256, 256>), grid, block, 0, stream, p); break;
     case 192: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 256, 192>), grid, block, 0, stream, p); break;
     case 128: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 128, 128>), grid, block, 0, stream, p); break;
@@ -811,7 +812,8 @@ int launch_set_rng(uint64_t seed, uint64_t offset, uint64_t* dst, hipStream_t st
 }
 
 // KV-cache append (reference flash_fwd_kernel.h:640-720, the Append_KV branch, without rotary): one thread moves
-// 16 bytes of one new key row and the matching 16 bytes of the value row.
+// 16 bytes of one new key row and the matching 16 bytes of the value row (vnew == nullptr: the values are a view of the key rows on both sides --
+// the absorbed MLA cache -- and the key copy has written them).
 __global__ void __launch_bounds__(256) fa_kv_append_kernel(const KvAppendK p) {
   const int cpr = p.d / 8;                       // 16-B chunks per row
   const int per_b = p.s_new * p.h_k * cpr;
@@ -835,7 +837,7 @@ __global__ void __launch_bounds__(256) fa_kv_append_kernel(const KvAppendK p) {
     unsigned short* kd = (unsigned short*)p.kcache + koff + (int64_t)hk * p.kc_hs + c * 8;
     unsigned short* vd = (unsigned short*)p.vcache + voff + (int64_t)hk * p.vc_hs + c * 8;
     *reinterpret_cast<u32x4*>(kd) = *reinterpret_cast<const u32x4*>(ks);
-    *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
+    if (p.vnew) *reinterpret_cast<u32x4*>(vd) = *reinterpret_cast<const u32x4*>(vs);
   }
 }
 

@@ -39,7 +39,7 @@ const Knobs& knobs();
 
 // What the last fa_fwd* / fa_bwd* call of this thread launched (fa_last_schedule in the C ABI).
 struct LastSchedule {
-  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel, 5 fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel
+  int fwd_kernel;   // 0 none, 1 fa_fwd_kernel (lock-step), 2 fa_fwd_il_kernel (pipelined), 3 fa_fwd_w64_kernel, 4 fa_fwd_fp8_kernel, 5 fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel, 7 fa_fwd_mla_kernel
   int fwd_nw;       // waves per workgroup (16 = 8-wave ping-pong)
   int fwd_feat;     // FEAT_* variant of the lock-step kernel
   int fwd_splits;   // split-KV factor
@@ -141,6 +141,12 @@ int launch_fwd_fp8_kv(const FwdK& p, const Fp8K& f8, int d, hipStream_t stream);
 // Forward for a v / o head dim of its own (fa_fwd_dv.hip): q / k head dim d = 192, v / o head dim dv = 128; 4 waves, 128 query rows and 80 KB of LDS per
 // workgroup, two workgroups per CU.  Plain attention (masks, GQA, packed batches, seqused_q / seqused_k).  -2 = pair not built.
 int launch_fwd_dv(const FwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
+
+// Absorbed MLA decode (fa_fwd_mla.hip): q / k head dim d = 576, v / o head dim dv = 512, v = the first 512 channels of the k row (FwdK::v is not read);
+// 4 waves, 64 packed rows and 144 KB of LDS per workgroup, one workgroup per CU.  seqused_k / kv_batch_idx / block_table / pack_g (always the packed
+// layout, g >= 1) / n_splits of FwdK as the lock-step kernel reads them, partial rows of width dv; with n_splits > 1 the caller runs
+// launch_splitkv_combine (d = 512) behind it.  -2 = pair not built.
+int launch_fwd_mla(const FwdK& p, int dtype_bf16, int d, int dv, hipStream_t stream);
 
 // Backward: delta = rowsum(dO*O) pre-pass, dK/dV kernel (loops over query blocks),
 // dQ kernel (loops over key blocks).  Same return convention.

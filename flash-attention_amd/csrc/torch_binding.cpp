@@ -485,11 +485,23 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
   }
   const int64_t B = q.size(0), Sq = q.size(1), H = q.size(2), D = q.size(3);
   const int64_t Hk = kcache.size(2);
-  TORCH_CHECK(vcache.size(-1) == D, "fwd_kvcache: head dims (", D, ", ", vcache.size(-1), "): the KV-cache path has no kernel for a v head dim that differs from q / k");
+  // The absorbed MLA decode pair (C ABI: fa_fwd_kvcache with d = 576, d_v = 512; csrc/fa_fwd_mla.hip): vcache must be the view kcache[..., :512]
+  const int64_t Dv = vcache.size(-1);
+  const bool mla = D == 576 && Dv == 512;
+  TORCH_CHECK(mla || Dv == D, "fwd_kvcache: head dims (", D, ", ", Dv, "): the KV-cache path has no kernel for a v head dim that differs from q / k");
   const int64_t page = paged ? kcache.size(1) : 0;
   const int64_t Sk = paged ? block_table_->size(1) * page : kcache.size(1);
   TORCH_CHECK(B > 0, "batch size must be positive");
-  TORCH_CHECK(D <= 256, "FlashAttention forward only supports head dimension at most 256");
+  TORCH_CHECK(mla || D <= 256, "FlashAttention forward only supports head dimension at most 256");
+  if (mla) {
+    TORCH_CHECK(!rotary_cos_.has_value() && !rotary_sin_.has_value(), "fwd_kvcache: head dims (576, 512) do not support rotary_cos / rotary_sin (MLA rotates the last 64 channels: rotate outside the call)");
+    TORCH_CHECK(!leftpad_k_.has_value(), "fwd_kvcache: head dims (576, 512) do not support leftpad_k (cache_leftpad)");
+    TORCH_CHECK(!alibi_slopes_.has_value(), "fwd_kvcache: head dims (576, 512) do not support ALiBi (alibi_slopes)");
+    TORCH_CHECK(!(softcap > 0.0), "fwd_kvcache: head dims (576, 512) do not support softcap");
+    TORCH_CHECK(vcache.dim() == 4 && kcache.dim() == 4 && vcache.data_ptr() == kcache.data_ptr() && vcache.stride(0) == kcache.stride(0) && vcache.stride(1) == kcache.stride(1) &&
+                vcache.stride(2) == kcache.stride(2) && vcache.size(0) == kcache.size(0) && vcache.size(1) == kcache.size(1) && vcache.size(2) == kcache.size(2),
+                "fwd_kvcache: head dims (576, 512): v_cache must be the first 512 channels of k_cache (the view k_cache[..., :512]); a separate V tensor is not supported");
+  }
   if (D % 8 != 0) {
     // flash_api.cpp:1340-1350, 1517-1527: q and BOTH caches are zero-padded to the next multiple of 8 (copies of the whole cache -- "we don't expect
     // to get this case in practice", the reference says of it), the call runs on the copies, and appended keys / values are copied back.
@@ -512,7 +524,7 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
     return {out, r[1]};
   }
   TORCH_CHECK(H % Hk == 0, "Number of heads in key/value must divide number of heads in query");
-  TORCH_CHECK(kcache.size(3) == D && vcache.sizes() == kcache.sizes(), "kcache / vcache shape mismatch");
+  TORCH_CHECK(kcache.size(3) == D && (mla || vcache.sizes() == kcache.sizes()), "kcache / vcache shape mismatch");
   if (paged) {
     TORCH_CHECK(page % 256 == 0, "Paged KV cache block size must be divisible by 256");
   } else if (!cache_batch_idx_.has_value()) {
@@ -562,13 +574,19 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
   }
   if (Sq == 1) window_size_right = -1;  // a right bound cannot hide a key from the single, bottom-right aligned query row
   if (k_.has_value()) {  // append first (flash_fwd_kernel.h Append_KV branch)
-    TORCH_CHECK(v_.has_value(), "If key is supplied, value must also be passed in");
+    TORCH_CHECK(mla || v_.has_value(), "If key is supplied, value must also be passed in");
     TORCH_CHECK(seqlens_k_.has_value(), "If key is supplied, seqlens_k must also be passed in");
-    const Tensor &kn = rotary_cos_.has_value() ? k_rot : *k_, &vn = *v_;
+    const Tensor& kn = rotary_cos_.has_value() ? k_rot : *k_;
+    TORCH_CHECK(kn.dim() == 4, "key must be 4-D");
+    // (576, 512): the new values are the first 512 channels of the new key rows -- v = None or that very view; the rows are written once
+    const Tensor vn = v_.has_value() ? *v_ : kn.slice(-1, 0, 512);
+    if (mla)
+      TORCH_CHECK(vn.dim() == 4 && vn.size(-1) == 512 && vn.data_ptr() == kn.data_ptr() && vn.stride(0) == kn.stride(0) && vn.stride(1) == kn.stride(1) && vn.stride(2) == kn.stride(2),
+                  "fwd_kvcache: head dims (576, 512): v must be None or the first 512 channels of k (the view k[..., :512]); a separate V tensor is not supported");
     TORCH_CHECK(kn.dtype() == q.dtype() && vn.dtype() == q.dtype(), "Key and value must have the same dtype as query");
     CHECK_DEVICE(kn); CHECK_DEVICE(vn); CHECK_LAST_CONTIG(kn); CHECK_LAST_CONTIG(vn);
     s_new = kn.size(1);
-    CHECK_SHAPE(kn, B, s_new, Hk, D); CHECK_SHAPE(vn, B, s_new, Hk, D);
+    CHECK_SHAPE(kn, B, s_new, Hk, D); CHECK_SHAPE(vn, B, s_new, Hk, Dv);
     FaKvAppendParams ap{};
     ap.knew = kn.data_ptr(); ap.vnew = vn.data_ptr(); ap.kcache = kcache.data_ptr(); ap.vcache = vcache.data_ptr();
     ap.knew_batch_stride = kn.stride(0); ap.knew_row_stride = kn.stride(1); ap.knew_head_stride = kn.stride(2);
@@ -586,20 +604,22 @@ std::vector<Tensor> mha_fwd_kvcache(Tensor& q, const Tensor& kcache, const Tenso
 
   // Decode trick of the reference (flash_api.cpp:1346-1353): with one query row the query heads of a KV group
   // become the rows of the score matrix, so K/V are streamed once per KV head.
-  const bool swap = Sq == 1 && H > Hk && window_size_left < 0 && !alibi_slopes_.has_value();
+  // (not for (576, 512): fa_fwd_mla_kernel packs the heads of a group into rows itself, for any query count)
+  const bool swap = Sq == 1 && H > Hk && window_size_left < 0 && !alibi_slopes_.has_value() && !mla;
   const int64_t ratio = H / Hk;
   Tensor qk = swap ? q_in.reshape({B, Hk, ratio, D}).transpose(1, 2) : q_in;  // (B, rows, heads, D)
   const int64_t rows = swap ? ratio : Sq, heads = swap ? Hk : H;
   Tensor out;
   if (out_.has_value() && !swap) {
     TORCH_CHECK(out_->dtype() == q.dtype(), "Output must have the same dtype as inputs");
-    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, B, Sq, H, D);
+    CHECK_DEVICE(*out_); CHECK_LAST_CONTIG(*out_); CHECK_SHAPE(*out_, B, Sq, H, Dv);
     out = *out_;
   } else {
-    out = at::empty({B, rows, heads, D}, q.options());
+    out = at::empty({B, rows, heads, Dv}, q.options());
   }
   Tensor lse = at::empty({B, heads, rows}, q.options().dtype(at::kFloat));
   FaFwdParams a{};
+  a.d_v = mla ? 512 : 0;
   a.q = qk.data_ptr(); a.k = kcache.data_ptr(); a.v = vcache.data_ptr(); a.o = out.data_ptr(); a.softmax_lse = lse.data_ptr<float>();
   a.q_batch_stride = qk.stride(0); a.q_row_stride = qk.stride(1); a.q_head_stride = qk.stride(2);
   a.k_batch_stride = kcache.stride(0); a.k_row_stride = kcache.stride(1); a.k_head_stride = kcache.stride(2);

@@ -27,8 +27,30 @@ def reload_knobs() -> None:
 
 _SCHED_FIELDS = ("fwd_kernel", "fwd_nw", "fwd_feat", "fwd_splits", "fwd_list", "d", "bf16", "bwd_dq_nw", "bwd_list", "bwd_spill", "fwd_pack", "bwd_dkdv_nw", "dv")
 FWD_KERNEL_NAMES = {0: "none", 1: "fa_fwd_kernel", 2: "fa_fwd_il_kernel", 3: "fa_fwd_w64_kernel", 4: "fa_fwd_fp8_kernel", 5: "fa_fwd_fp8_kv_kernel",
-                    6: "fa_fwd_dv_kernel"}
+                    6: "fa_fwd_dv_kernel", 7: "fa_fwd_mla_kernel"}
 HEAD_DIM_PAIRS = ((192, 128),)  # (q / k head dim, v / o head dim) pairs built besides Dv = D (csrc/fa_api.cpp check_value_dim)
+# The absorbed MLA decode shape is kept OUT of HEAD_DIM_PAIRS on purpose: that tuple gates fwd / varlen_fwd / bwd (check_head_dim_pair), which refuse
+# (576, 512); the pair runs on fwd_kvcache only, with v_cache = k_cache[..., :512] (csrc/fa_fwd_mla.hip).
+MLA_DECODE_PAIR = (576, 512)
+
+
+def is_latent_view(v, k) -> bool:
+    """v is the first 512 channels of k's rows: the same memory, the same batch / row / head strides."""
+    if not (v.dim() == 4 and k.dim() == 4 and v.shape[:3] == k.shape[:3] and v.shape[-1] == MLA_DECODE_PAIR[1] and v.stride() == k.stride()
+            and v.storage_offset() == k.storage_offset()):
+        return False
+    try:
+        return v.data_ptr() == k.data_ptr()
+    except RuntimeError:   # fake tensors have no address: shapes, strides and offsets have been compared
+        return True
+
+
+def check_mla_decode(fn: str, *, rotary=False, leftpad_k=False, alibi_slopes=False, softcap=0.0) -> None:
+    """Refusals of the (576, 512) pair on the KV-cache path, on flags alone (the C ABI's check_value_dim; rotary is the binders')."""
+    for bad, what in ((rotary, "rotary_cos / rotary_sin (MLA rotates the last 64 channels: rotate outside the call)"), (leftpad_k, "leftpad_k (cache_leftpad)"),
+                      (alibi_slopes, "ALiBi (alibi_slopes)"), (softcap > 0.0, "softcap")):
+        if bad:
+            raise RuntimeError(f"{fn}: head dims (576, 512) do not support {what}")
 
 
 def last_schedule() -> dict:
@@ -628,12 +650,26 @@ def fwd_kvcache(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
             raise RuntimeError("rotary_cos/sin must have contiguous last dimension and equal row strides")
     B, Sq, H, D = q.shape
     Hk = kcache.shape[2]
-    if vcache.shape[-1] != D:
+    Dv = vcache.shape[-1]
+    mla = (D, Dv) == MLA_DECODE_PAIR
+    if Dv != D and not mla:
         raise RuntimeError(f"fwd_kvcache: head dims ({D}, {vcache.shape[-1]}): the KV-cache path has no kernel for a v head dim that differs from q / k")
     page = kcache.shape[1] if paged else 0
     Sk = block_table_.shape[1] * page if paged else kcache.shape[1]
-    if D > 256:
+    if D > 256 and not mla:
         raise RuntimeError("FlashAttention forward only supports head dimension at most 256")
+    if mla:
+        check_mla_decode("fwd_kvcache", rotary=rotary_cos_ is not None or rotary_sin_ is not None, leftpad_k=leftpad_k_ is not None,
+                         alibi_slopes=alibi_slopes_ is not None, softcap=softcap)
+        if not is_latent_view(vcache, kcache):
+            raise RuntimeError("fwd_kvcache: head dims (576, 512): v_cache must be the first 512 channels of k_cache (the view k_cache[..., :512]); "
+                               "a separate V tensor is not supported")
+        if k_ is not None:
+            if v_ is None:
+                v_ = k_[..., :Dv]   # the new values are the latent part of the new key rows; the rows are written once
+            elif not is_latent_view(v_, k_):
+                raise RuntimeError("fwd_kvcache: head dims (576, 512): v must be None or the first 512 channels of k (the view k[..., :512]); "
+                                   "a separate V tensor is not supported")
     if D % 8 != 0:
         # flash_api.cpp:1340-1350, 1517-1527: q and both caches zero-padded to the next multiple of 8 (whole-cache copies, as in the reference), the call
         # runs on the copies, appended keys / values are copied back
@@ -688,11 +724,12 @@ def fwd_kvcache(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
             _cabi.check(lib.fa_kvcache_append(C.byref(ap), C.c_void_p(_stream_ptr(q.device))))
         if Sq == 1:
             window_size_right = -1  # a right bound cannot hide a key from the single, bottom-right aligned query row
-        swap = Sq == 1 and H > Hk and window_size_left < 0 and alibi_slopes_ is None
+        # (not for (576, 512): fa_fwd_mla_kernel packs the heads of a group into rows itself, for any query count)
+        swap = Sq == 1 and H > Hk and window_size_left < 0 and alibi_slopes_ is None and not mla
         ratio = H // Hk
         qk = q.reshape(B, Hk, ratio, D).transpose(1, 2) if swap else q
         rows, heads = (ratio, Hk) if swap else (Sq, H)
-        out = out_ if (out_ is not None and not swap) else torch.empty((B, rows, heads, D), dtype=q.dtype, device=q.device)
+        out = out_ if (out_ is not None and not swap) else torch.empty((B, rows, heads, Dv), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, heads, rows), dtype=torch.float32, device=q.device)
         alibi, alibi_bs = _alibi_args(alibi_slopes_, B, H)
         a = _cabi.FaFwdParams()
@@ -706,6 +743,7 @@ def fwd_kvcache(q, kcache, vcache, k_, v_, seqlens_k_, rotary_cos_, rotary_sin_,
         a.block_table_batch_stride, a.page_block_size = (block_table_.stride(0) if paged else 0), page
         a.alibi_slopes, a.alibi_batch_stride = _ptr(alibi), alibi_bs
         a.b, a.h, a.h_k, a.d = B, heads, Hk, D
+        a.d_v = Dv if mla else 0
         a.seqlen_q, a.seqlen_k, a.total_q = rows, Sk, B * rows
         a.dtype = _dtype_code(q)
         a.is_causal, a.window_left, a.window_right = int(bool(is_causal)), int(window_size_left), int(window_size_right)

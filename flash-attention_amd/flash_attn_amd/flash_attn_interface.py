@@ -596,11 +596,30 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     first valid cache row of each entry.  No backward.
     float8_e4m3fn q / caches / new k, v (FA3's fp8 KV cache): optional fp32 (B, Hk) ``q_descale`` / ``k_descale`` / ``v_descale`` indexed by the
     batch entry of q, bf16 out, head dims 64 / 128; new keys / values are appended as bytes (quantise them with the cache's scale); rotary,
-    ``cache_leftpad``, ALiBi and softcap are refused."""
+    ``cache_leftpad``, ALiBi and softcap are refused.
+    Absorbed MLA decode (DeepSeek-V2/V3): q (B,Sq,H,576) against a latent cache k_cache (.., Hk, 576) -- 512 latent + 64 rotary channels -- with
+    ``v_cache = k_cache[..., :512]``, the SAME memory (a separate V tensor is refused): every cache row is read once, out is (B,Sq,H,512), the
+    default softmax_scale is 576 ** -0.5.  bf16 / fp16; ``cache_seqlens``, ``cache_batch_idx``, ``block_table``, masks, ``num_splits`` as above; new
+    rows ``k`` (B,S_new,Hk,576) with ``v`` None or ``k[..., :512]`` are written once; rotary (rotate the last 64 channels outside the call),
+    ``cache_leftpad``, ALiBi, softcap and fp8 are refused."""
     q, k, v = (_unit_stride_last(t) for t in (q, k, v))
-    _refuse_head_dims("flash_attn_with_kvcache", q.shape[-1], v_cache.shape[-1], "the KV-cache path")
     fp8 = (q.dtype == torch.float8_e4m3fn or k_cache.dtype == torch.float8_e4m3fn or v_cache.dtype == torch.float8_e4m3fn
            or q_descale is not None or k_descale is not None or v_descale is not None)
+    from . import backend as _be
+    mla = (q.shape[-1], v_cache.shape[-1]) == _be.MLA_DECODE_PAIR
+    if mla and fp8:
+        raise RuntimeError("flash_attn_with_kvcache: head dims (576, 512): the fp8 KV cache has no kernel for a v head dim that differs from q / k")
+    if mla:   # shapes and flags only, before the backend is reached
+        _be.check_mla_decode("flash_attn_with_kvcache", rotary=rotary_cos is not None or rotary_sin is not None, leftpad_k=cache_leftpad is not None,
+                             alibi_slopes=alibi_slopes is not None, softcap=softcap)
+        if not _be.is_latent_view(v_cache, k_cache):
+            raise RuntimeError("flash_attn_with_kvcache: head dims (576, 512): v_cache must be the first 512 channels of k_cache (the view "
+                               "k_cache[..., :512]); a separate V tensor is not supported")
+        if k is not None and v is not None and not _be.is_latent_view(v, k):
+            raise RuntimeError("flash_attn_with_kvcache: head dims (576, 512): v must be None or the first 512 channels of k (the view k[..., :512]); "
+                               "a separate V tensor is not supported")
+    else:
+        _refuse_head_dims("flash_attn_with_kvcache", q.shape[-1], v_cache.shape[-1], "the KV-cache path")
     if fp8:
         _fp8_kvcache_route(q, k_cache, v_cache, k, v, rotary_cos, rotary_sin, cache_leftpad, softcap, alibi_slopes, (q_descale, k_descale, v_descale))
     if softmax_scale is None:

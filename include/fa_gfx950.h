@@ -36,6 +36,15 @@
  *     causal / window masks, MHA / GQA / MQA, seqused_q / seqused_k; softmax_scale is the caller's -- the binders default to d ** -0.5, d = q's head dim).  Any
  *     other pair with d_v != d, and this pair with dropout, softcap, ALiBi, return_softmax, block_table, leftpad_k, a KV cache or FP8, returns
  *     FA_ERR_UNSUPPORTED with a message naming both head dims or the argument;
+ *   - absorbed MLA decode (fa_fwd_kvcache only): d = 576 with d_v = 512 -- q (B,Sq,H,576), a latent cache k (.., Hk, 576) = 512 latent + 64 rotary channels,
+ *     o (B,Sq,H,512) -- where v IS the first 512 channels of the k rows: the caller passes the view k_cache[..., :512], i.e. v == k with equal batch / row /
+ *     head strides, and every cache row is read from HBM once for both products.  Anything else as v returns FA_ERR_UNSUPPORTED ("V must be the first 512
+ *     channels of K").  bf16 / fp16, any H % Hk == 0 (the query heads of a KV group are always packed into the rows of 64-row blocks), any seqlen_q, k row
+ *     stride >= 576, all q / k / o strides multiples of 8 elements, q / k 16-byte aligned; seqused_k (+ seqused_k_add), cache_batch_idx, block_table (pages
+ *     of a multiple of 256 keys), causal / window masks aligned to each entry's own length, num_splits with fp32 partials of width 512
+ *     (fa_fwd_workspace_bytes: (512 + 1) * 4 bytes per row and split; keys are split while H / Hk * seqlen_q <= 128).  FA_ERR_UNSUPPORTED naming (576, 512)
+ *     or the argument for leftpad_k, ALiBi, softcap, the fp8 entry points, fa_fwd / fa_varlen_fwd and the backward; d = 576 with d_v = 0 or 576 stays
+ *     "at most 256".  At most 64 key splits (as on every KV-cache path: the merge reads one split per lane).  fa_kvcache_append writes such rows once (below);
  *   - return value 0 = enqueued; negative = FA_ERR_* (message via fa_last_error()).
  */
 #ifndef FA_GFX950_H_
@@ -91,8 +100,9 @@ typedef struct FaFwdParams {
   int32_t page_block_size;          /* keys per page, multiple of 256 (reference flash_api.cpp:1318)  */
   int32_t num_splits;               /* fa_fwd_kvcache: 0 = heuristic, 1 = no split, >1 = split the keys this many ways */
   float p_dropout;                  /* probability to DROP, in [0, 1); 0 = off                         */
-  int32_t d_v;                      /* head dim of v / o when it differs from d (took the place of a reserved field; 0 = d).  fa_fwd / fa_varlen_fwd only,
-                                       and only the pair d = 192, d_v = 128 (DeepSeek-V2/V3 multi-head latent attention: 128 "nope" + 64 rotary q/k
+  int32_t d_v;                      /* head dim of v / o when it differs from d (took the place of a reserved field; 0 = d).  fa_fwd_kvcache: only d = 576,
+                                       d_v = 512 with v == k (see above).  fa_fwd / fa_varlen_fwd:
+                                       only the pair d = 192, d_v = 128 (DeepSeek-V2/V3 multi-head latent attention: 128 "nope" + 64 rotary q/k
                                        channels, 128 v channels; the reference's hopper/flash_api.cpp:782-786): v is (.., Hk, d_v), o (.., H, d_v) */
   /* dropout (p_dropout > 0): */
   const uint64_t* rng_state;        /* device, 2 x u64 {seed, offset} (reference rng_state, flash_api.cpp:496-515) */
@@ -115,7 +125,9 @@ typedef struct FaFwdParams {
 } FaFwdParams;
 
 /* Append step of the KV-cache path: copy knew/vnew (B, S_new, Hk, D) into the cache at rows
- * seqlens_k[b] .. seqlens_k[b]+S_new-1 of cache row cache_batch_idx[b] (or page-table addressed). */
+ * seqlens_k[b] .. seqlens_k[b]+S_new-1 of cache row cache_batch_idx[b] (or page-table addressed).
+ * For ANY dtype and d: when vnew == knew and vcache == kcache with equal batch / row / head strides on both sides (the values are a view of the key
+ * rows, e.g. the absorbed MLA cache), the key copy has written every byte and the V copy is skipped -- such a call used to write the same bytes twice. */
 typedef struct FaKvAppendParams {
   const void* knew;
   const void* vnew;
@@ -233,7 +245,7 @@ void fa_knobs_reload(void);
 /* Which kernels the calling thread's last fa_fwd* / fa_bwd* call enqueued (for tests and the benchmark's labels; the
  * reference exposes nothing comparable -- its dispatch is compile-time, flash_fwd_launch_template.h).  Fills up to n of
  * FA_SCHEDULE_FIELDS int32: {forward kernel id (0 none, 1 lock-step fa_fwd_kernel, 2 pipelined fa_fwd_il_kernel,
- * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel, 5 FP8 KV-cache fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel: v / o head dim of its own), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
+ * 3 64-rows-per-wave fa_fwd_w64_kernel, 4 FP8 fa_fwd_fp8_kernel, 5 FP8 KV-cache fa_fwd_fp8_kv_kernel, 6 fa_fwd_dv_kernel: v / o head dim of its own, 7 fa_fwd_mla_kernel: absorbed MLA decode 576 / 512), waves per workgroup (16 = 8-wave ping-pong), feature variant, key splits,
  * varlen work list used, head dim, bf16, dQ-kernel waves, backward work lists used, backward spilled dS (5 contractions),
  * query heads packed into the rows of a block (fa_fwd_kvcache, 1 = none), dK/dV schedule (8 waves x 32 keys, 4 at head dim 256,
  * or 64 = 4 waves x 64 keys), head dim of v / o (= head dim unless FaFwdParams::d_v set it)}; returns FA_SCHEDULE_FIELDS (fields are only ever appended). */
@@ -278,7 +290,7 @@ int fa_varlen_fwd_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* s
  * fa_rotary refuses e4m3 (rotating quantised values needs a requantisation nobody has defined). */
 int fa_fwd_kvcache_fp8(const FaFwdParams* params, const FaFp8Params* fp8, void* stream);
 /* Inference forward against a KV cache: fa_fwd plus seqused_k (cache_seqlens), cache_batch_idx and/or a
- * paged cache (block_table).  k/v point at the cache.  No backward. */
+ * paged cache (block_table).  k/v point at the cache.  No backward.  d = 576, d_v = 512, v == k: the absorbed MLA decode (Conventions above). */
 int fa_fwd_kvcache(const FaFwdParams* params, void* stream);
 /* Writes the new keys/values into the cache (call before fa_fwd_kvcache with seqused_k_add = seqlen_new). */
 int fa_kvcache_append(const FaKvAppendParams* params, void* stream);
