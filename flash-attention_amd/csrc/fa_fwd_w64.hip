@@ -36,6 +36,16 @@
 //   * Q / O through buffer descriptors with 32-bit lane offsets (hoisted 64-bit addresses were spilled: a scratch reload waits on vmcnt(0),
 //     i.e. on every tile DMA in flight), the next block's Q trickled in a piece per iteration, block id carried from that prefetch; O zeroed
 //     by eight MFMAs, accumulator reads eight per asm statement (hipcc pads every asm statement with an s_nop).
+//
+// Round 7: fewer instruction BYTES in the once-per-block code, which is instruction-fetch-bound (~26 clocks per 64-byte line, profiles/r04_fwd_w64_per_block_code.txt;
+// before / after per part: profiles/r07_fwd_w64_block_code.txt).  The tile loop is untouched.
+//   * block decode without a divide: the five divisors (unit_size, unit_hpx, nmb, h, hk_ratio) are launch constants, the launcher passes multiply-shift reciprocals
+//     (FwdK::rc, six words read from the kernel-argument segment at decode time; fa_kernel_params.h fastdiv / fwd_w64_decode -- the same vb -> (batch, head, query block) map,
+//     walked on the CPU by tests/test_w64_decode_cpu.py);
+//   * a DENSE instantiation of the plain kernel for fixed-length batches without a left window: no per-block tests and loads of cu_seqlens / seqused / leftpad /
+//     kv_batch_idx / work list, no left limits, no two-sided ranges;
+//   * a masked iteration followed by the wave's peeled last one does not restore the mask broadcasts (nobody reads them again).
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -116,10 +126,15 @@ template <typename E, int T> FA_DEVINL void mfma_o_acc(u32x4 a, u32x4 b) {
 // descriptor -- base = pool + table[b][page] * page_stride + the tile's rows inside the page, range = the tile's rows that exist -- made from scalars at the
 // head of its iteration (~30 scalar instructions per iteration); the table entry of the tile after next is requested one iteration ahead.  Pools of any size
 // (the 32-bit offsets only span a tile).  Plain attention only.
-template <typename E, int D, int FEAT = 0, bool PAGED = false>
+//
+// DENSE (round 7) = a fixed-length batch without a left window: no cu_seqlens, seqused, leftpad_k, kv_batch_idx or work list (the launcher checks).  Per-block code is paid
+// for by the instruction byte (profiles/r04_fwd_w64_per_block_code.txt), and such a batch needs none of the per-block tests and loads of those arrays, no left
+// limits and no two-sided ranges: they are compiled out.  Everything else is the one shared body.  Plain attention only.
+template <typename E, int D, int FEAT = 0, bool PAGED = false, bool DENSE = false>
 __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
   constexpr bool ALIBI = FEAT == FEAT_ALIBI;
   static_assert(!PAGED || FEAT == 0, "the paged variant serves plain attention");
+  static_assert(!DENSE || (FEAT == 0 && !PAGED), "the dense variant serves plain attention on contiguous keys / values");
   constexpr bool SOFTCAP = FEAT == FEAT_CAP;
   constexpr bool DROP = FEAT == FEAT_DROP;
   constexpr bool DESC = ALIBI;   // iteration u scores key tile n_tiles - 1 - u instead of tile u
@@ -157,31 +172,40 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
   // dynamically; a static walk has to do it by construction).
   struct Blk { int b, h, m_block, sq, sk; int64_t q_row0, k_row0, q_boff, k_boff, v_boff, o_boff; };
   const int n_virtual = p.persist_total > 0 ? p.persist_total : (int)gridDim.x;
-  const bool snake = p.persist_total > 0 && p.wr >= 0 && p.unit_size > 1 && ((int)(gridDim.x / 8) % p.unit_size) == 0;
+  // the decode's reciprocals (FwdK::rc) are READ from the kernel-argument segment where a block is decoded: as kernel arguments held in registers they were ten (packed: six)
+  // more scalars live across the tile loop, and the feature variants paid for them in scalar spills
+  auto load_rc = [&]() __attribute__((always_inline)) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));   // (laundered: a load through the plain pointer is folded into the argument loads at the kernel's entry)
+    const uint32_t __attribute__((address_space(4)))* w = (const uint32_t __attribute__((address_space(4)))*)(ka + offsetof(FwdK, rc));
+    W64Rc r;
+    r.mul[0] = w[0]; r.mul[1] = w[1]; r.mul[2] = w[2]; r.mul[3] = w[3]; r.mul[4] = w[4]; r.shifts = w[5];
+    return r;
+#else
+    return p.rc;
+#endif
+  };
+  const W64Rc rc0 = load_rc();
+  const int g8 = (int)(gridDim.x >> 3);
+  const bool snake = p.persist_total > 0 && p.wr >= 0 && p.unit_size > 1 && g8 - fastdiv(g8, rc_get(rc0, RC_UNIT)) * p.unit_size == 0;
   // decode_id: virtual block -> (batch, head, query block): the divisions, done ONCE per block (the id of the next block is carried
   // over from the Q prefetch); fill_blk: lengths and offsets of a block, cheap
-  auto decode_id = [&](int vb, int round, Blk& k) __attribute__((always_inline)) -> bool {
+  auto decode_id = [&](const W64Rc& rc, int vb, int round, Blk& k) __attribute__((always_inline)) -> bool {
     if (vb >= n_virtual) return false;
-    if (p.work_list) {  // varlen: non-empty blocks only, heaviest first (fa_varlen_schedule_kernel)
+    if (!DENSE && p.work_list) {  // varlen: non-empty blocks only, heaviest first (fa_varlen_schedule_kernel)
       if (!work_list_item(p.work_list, vb, p.h, p.h_k, k.b, k.h, k.m_block)) return false;
     } else {
-      int bid = vb;
-      if (snake && (round & 1)) {   // same unit, mirrored item
-        const int slot = vb / 8, item = slot % p.unit_size;
-        bid = vb + 8 * (p.unit_size - 1 - 2 * item);
-      }
-      const int w = xcd_interleave(bid, p.n_units, p.unit_size, p.unit_hpx);
-      if (w < 0) return false;
-      const int bh = w / p.nmb;
-      const int mbr = w - bh * p.nmb;
-      k.m_block = (p.wr >= 0) ? (p.nmb - 1 - mbr) : mbr;
-      k.b = bh / p.h;
-      k.h = bh - k.b * p.h;
+      if (!fwd_w64_decode(p, rc, vb, snake && (round & 1), k.b, k.h, k.m_block)) return false;
     }
     return true;
   };
   auto fill_blk = [&](Blk& k) __attribute__((always_inline)) -> bool {
     k.sq = p.sq; k.sk = p.sk; k.q_row0 = 0; k.k_row0 = 0;
+    if constexpr (DENSE) {   // the batch offsets, nothing else
+      k.q_boff = (int64_t)k.b * p.q_bs; k.k_boff = (int64_t)k.b * p.k_bs; k.v_boff = (int64_t)k.b * p.v_bs; k.o_boff = (int64_t)k.b * p.o_bs;
+      return k.m_block * BM < k.sq;
+    }
     const int bkv = p.kv_batch_idx ? p.kv_batch_idx[k.b] : k.b;
     k.q_boff = (int64_t)k.b * p.q_bs; k.k_boff = (int64_t)bkv * p.k_bs; k.v_boff = (int64_t)bkv * p.v_bs; k.o_boff = (int64_t)k.b * p.o_bs;
     if (p.cu_q) { const int c0 = p.cu_q[k.b]; k.sq = p.cu_q[k.b + 1] - c0; k.q_row0 = c0; k.q_boff = 0; k.o_boff = 0; }
@@ -240,34 +264,35 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
     voff_l[i] = (unsigned)(row * (int)p.v_rs + vc * 8) * 2u - (unsigned)(i * 1024);
   }
   const float thr = p.rescale_thr;
-  const bool two_sided = p.wl >= 0;
+  const bool has_wl = !DENSE && p.wl >= 0;   // a left bound
 
   Blk cur_id;
   cur_id.b = 0; cur_id.h = 0; cur_id.m_block = 0;
-  bool cur_ok = decode_id((int)blockIdx.x, 0, cur_id);
+  bool cur_ok = decode_id(rc0, (int)blockIdx.x, 0, cur_id);
   for (int vb = blockIdx.x, round = 0; vb < n_virtual; vb += gridDim.x, ++round) {
   Blk blk = cur_id, nxt;
   const bool blk_ok = cur_ok && fill_blk(blk);
   nxt.b = 0; nxt.h = 0; nxt.m_block = 0;
-  const bool nxt_id_ok = p.persist_total > 0 && decode_id(vb + (int)gridDim.x, round + 1, nxt);
+  const W64Rc rc = load_rc();
+  const bool nxt_id_ok = p.persist_total > 0 && decode_id(rc, vb + (int)gridDim.x, round + 1, nxt);
   cur_id.b = __builtin_amdgcn_readfirstlane(nxt.b); cur_id.h = __builtin_amdgcn_readfirstlane(nxt.h); cur_id.m_block = __builtin_amdgcn_readfirstlane(nxt.m_block);
   cur_ok = nxt_id_ok;   // (scalar on purpose: carried in vector registers the three values end up in scratch)
   if (!blk_ok) continue;   // (uniform over the workgroup: no barrier is skipped by part of it)
   const int b = blk.b, h = blk.h, m_block = blk.m_block, sq = blk.sq, sk = blk.sk;
-  const int hk = h / p.hk_ratio;
+  const int hk = fastdiv(h, rc_get(rc, RC_HKR));
   const int64_t q_row0 = blk.q_row0, k_row0 = blk.k_row0, q_boff = blk.q_boff, k_boff = blk.k_boff, v_boff = blk.v_boff, o_boff = blk.o_boff;
   const int m0 = m_block * BM;
 
   const E* __restrict__ kp = (const E*)p.k + k_boff + k_row0 * p.k_rs + (int64_t)hk * p.k_hs;
   const E* __restrict__ vp = (const E*)p.v + v_boff + k_row0 * p.v_rs + (int64_t)hk * p.v_hs;
   E* __restrict__ op = (E*)p.o + o_boff + q_row0 * p.o_rs + (int64_t)h * p.o_hs;
-  float* __restrict__ lsep = p.cu_q ? (p.lse + (int64_t)h * p.total_q + q_row0) : (p.lse + ((int64_t)b * p.h + h) * p.sq);
+  float* __restrict__ lsep = (!DENSE && p.cu_q) ? (p.lse + (int64_t)h * p.total_q + q_row0) : (p.lse + ((int64_t)b * p.h + h) * p.sq);
 
   const int shift = sk - sq;
   const int blk_last = min(m0 + BM, sq) - 1;
   int kmax = sk - 1, kmin = 0;
   if (p.wr >= 0) kmax = min(kmax, blk_last + shift + p.wr);
-  if (p.wl >= 0) kmin = max(0, m0 + shift - p.wl);
+  if (has_wl) kmin = max(0, m0 + shift - p.wl);
   const int n_min = kmin / BN;
   const int n_max = (kmax >= kmin) ? (kmax / BN + 1) : n_min;
   const int n_tiles = n_max - n_min;
@@ -283,15 +308,15 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
   const int w_row1 = min(w_row0 + 63, sq - 1);
   const bool wave_valid = w_row0 < sq;
   const int w_kmax = (p.wr >= 0) ? min(sk - 1, w_row1 + shift + p.wr) : sk - 1;
-  const int w_kmin = (p.wl >= 0) ? max(0, w_row0 + shift - p.wl) : 0;
+  const int w_kmin = has_wl ? max(0, w_row0 + shift - p.wl) : 0;
   const int w_full_hi = (p.wr >= 0) ? min(sk - 1, w_row0 + shift + p.wr) : sk - 1;
-  const int w_full_lo = (p.wl >= 0) ? (w_row1 + shift - p.wl) : 0;
+  const int w_full_lo = has_wl ? (w_row1 + shift - p.wl) : 0;
   int lim_hi[QB], lim_lo[QB];
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const int my_row = w_row0 + 32 * qb + qi;
     lim_hi[qb] = (p.wr >= 0) ? min(sk - 1, my_row + shift + p.wr) : sk - 1;
-    lim_lo[qb] = (p.wl >= 0) ? max(0, my_row + shift - p.wl) : 0;   // (>= 0: the descending walk's drain step scores the zero tile left of key 0 -- it must not count as visible)
+    lim_lo[qb] = has_wl ? max(0, my_row + shift - p.wl) : 0;   // (>= 0: the descending walk's drain step scores the zero tile left of key 0 -- it must not count as visible)
   }
   // ---- K/V tiles: global -> LDS by DMA through a buffer descriptor.  The LDS image is lane-linear, so the XOR swizzles
   // are applied to the per-lane SOURCE chunk.  A wave issues its DPW pieces of a tile from ONE statement: M0 = LDS base
@@ -954,7 +979,18 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
     fast_step(ICw<0>{}, parc, sA, sB, pfA, pfB, srd_k, koff_l, tk_, dst_k, kring, DROP ? step_key(2 * us - 1) >> 2 : 0, M0{});
     if constexpr (PM != 2) { if (__builtin_expect(masked(), 0)) set_mask(2 * u + 1); }
     fast_step(ICw<1>{}, parc, sB, sA, pfB, pfA, srd_v, voff_l, tv_, dst_v, kring, DROP ? step_key(2 * us) >> 2 : 0, M1{});
-    if constexpr (PM != 2) { if (__builtin_expect(masked(), 0)) clear_mask(2 * u + 2); }
+    // (round 7) plain attention: the iteration after this one is the wave's peeled last one (PM == 2) when u + 1 == u_last -- it issues no score chain, so nobody reads the
+    // broadcasts again before the next block initialises them: the 32 rewrites are skipped.  Under a right bound that is every wave's diagonal iteration, i.e. four of a
+    // block's iterations (the waves reach theirs one after the other and meet a barrier in each).  A left window's masked iterations are followed by plain ones and keep it.
+    // (the second test sits INSIDE the cold branch, on a scalar laundered there: combined with the first it was five scalar instructions in every iteration, +25 clocks
+    // on the steady iteration, profiles/r07_fwd_w64_block_code.txt)
+    if constexpr (PM != 2) {
+      if (__builtin_expect(masked(), 0)) {
+        int to_last = FEAT == 0 ? u_last - 1 - us : 1;   // 0: the next iteration is the peeled last one
+        asm volatile("" : "+s"(to_last));
+        if (to_last != 0) clear_mask(2 * u + 2);
+      }
+    }
     iter_end();
   };
   auto idle_iter = [&](int u) __attribute__((always_inline)) {
@@ -1019,8 +1055,6 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
     static_for<DB>([&](auto dbc) __attribute__((always_inline)) {
       constexpr int db = decltype(dbc)::value;
       acc_read_tuple<16 * (qb * DB + db)>(o_v[db]);
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o_v[db][r] = o_v[db][r];
     });
     const float l_tot = half_sum(l_run[qb][0] + l_run[qb][1]);
     const bool dead = (l_tot == 0.f) || (l_tot != l_tot);
@@ -1061,11 +1095,15 @@ __global__ void __launch_bounds__(256, 1) fa_fwd_w64_kernel(const FwdK p) {
   }  // persistent block loop
 }
 
-template <typename E, int D, int FEAT = 0, bool PAGED = false>
+template <typename E, int D, int FEAT = 0, bool PAGED = false, bool DENSE = false>
 static int launch_fwd_w64_t(const FwdK& p, hipStream_t stream) {
+  if constexpr (FEAT == 0 && !PAGED && !DENSE) {   // plain attention: a fixed-length batch without a left window takes the dense variant
+    if (!p.cu_q && !p.cu_k && !p.seqused_q && !p.seqused_k && !p.leftpad_k && !p.kv_batch_idx && !p.work_list && p.wl < 0)
+      return launch_fwd_w64_t<E, D, 0, false, true>(p, stream);
+  }
   constexpr int STAGE = 256 * (D * 2 + 16);
   constexpr int smem = ((4 * 64 * D * 2 > STAGE ? 4 * 64 * D * 2 : STAGE + 1023) / 1024 * 1024) + 256 * D * 2;  // K/V buffers | O staging, then the Q block
-  auto kern = fa_fwd_w64_kernel<E, D, FEAT, PAGED>;
+  auto kern = fa_fwd_w64_kernel<E, D, FEAT, PAGED, DENSE>;
   static std::atomic<unsigned long long> attr_mask{0};  // the kernel addresses LDS by byte offset: the dynamic segment must start at 0
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;
   const long long total = p.work_list ? (long long)p.work_bound * p.h : units_grid(p.n_units, p.unit_size);
@@ -1073,6 +1111,7 @@ static int launch_fwd_w64_t(const FwdK& p, hipStream_t stream) {
   // dense grids larger than the chip: one persistent workgroup per CU walks the blocks (multiple of 8 keeps vb % 8 = XCD);
   // work lists keep one workgroup per block (their order is already heavy-first, the dispatcher balances the tail)
   FwdK pp = p;
+  fwd_w64_reciprocals(pp);
   long long grid = total;
   const int cus = device_cu_count();
   // (under a right-bounded mask the static walk is balanced by mirroring every other round inside its units: needs rounds
@@ -1089,6 +1128,7 @@ static int launch_fwd_w64_t(const FwdK& p, hipStream_t stream) {
   ls.bf16 = std::is_same<E, __bf16>::value;
   if (FEAT) snprintf(ls.name, sizeof(ls.name), "fa::fa_fwd_w64_kernel<%s,%d,%s>", ls.bf16 ? "bf16" : "f16", D, FEAT == FEAT_CAP ? "softcap" : FEAT == FEAT_DROP ? "dropout" : "alibi");
   else if (PAGED) snprintf(ls.name, sizeof(ls.name), "fa::fa_fwd_w64_kernel<%s,%d,paged>", ls.bf16 ? "bf16" : "f16", D);
+  else if (DENSE) snprintf(ls.name, sizeof(ls.name), "fa::fa_fwd_w64_kernel<%s,%d,dense>", ls.bf16 ? "bf16" : "f16", D);
   else snprintf(ls.name, sizeof(ls.name), "fa::fa_fwd_w64_kernel<%s,%d>", ls.bf16 ? "bf16" : "f16", D);
   return 0;
 }

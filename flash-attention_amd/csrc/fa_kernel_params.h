@@ -6,6 +6,32 @@
 
 namespace fa {
 
+// Division by a launch constant without a divide (gfx950 has none: `n / d` with a run-time d expands to a few dozen instructions).  For 1 <= d <= 2^31 and
+// 0 <= n < 2^31:  n / d == mulhi(2n, mul) >> shift  with shift = ceil(log2 d), mul = ceil(2^(31 + shift) / d) < 2^32 -- the error term n * (mul * d - 2^(31 + shift))
+// / (d * 2^(31 + shift)) stays below 1 / d because n < 2^31 and mul * d - 2^(31 + shift) < d <= 2^shift (tests/test_w64_decode_cpu.py walks it).  d <= 0 is kept as
+// "divide by one" (the caller never divides by such a value: unit_hpx = 0 selects the round-robin mapping).
+struct FastDiv { uint32_t mul, shift; };
+inline FastDiv fastdiv_make(int32_t d) {
+  FastDiv f = {0x80000000u, 0u};
+  if (d <= 1) return f;
+  while ((1ull << f.shift) < (uint64_t)d) ++f.shift;
+  f.mul = (uint32_t)(((1ull << (31 + f.shift)) + (uint64_t)d - 1) / (uint64_t)d);
+  return f;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int32_t fastdiv(int32_t n, FastDiv f) { return (int32_t)((uint32_t)(((uint64_t)((uint32_t)n << 1) * (uint64_t)f.mul) >> 32) >> f.shift); }
+// The five reciprocals of the fa_fwd_w64 block decode, packed: the multipliers, and the shifts (<= 31) six bits each in one word.  The kernel reads the six words
+// from its kernel-argument segment where it decodes a block, so they are not carried in registers across the tile loop (as ten live scalars they pushed up to
+// thirteen more scalar spills into the feature variants).
+enum { RC_UNIT = 0, RC_HPX = 1, RC_NMB = 2, RC_H = 3, RC_HKR = 4 };
+struct alignas(8) W64Rc { uint32_t mul[5]; uint32_t shifts; };
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline FastDiv rc_get(const W64Rc& r, int i) { FastDiv f = {r.mul[i], (r.shifts >> (6 * i)) & 63u}; return f; }
+
 struct FwdK {
   const void* q;
   const void* k;
@@ -57,7 +83,40 @@ struct FwdK {
   int64_t rv_bs, rv_hs, rv_rs;
   uint32_t drop_thr8;        // floor(255 * (1 - p_dropout))
   float rp_keep;             // 1 / (1 - p_dropout)
+  // fa_fwd_w64 (filled by its launcher, fwd_w64_reciprocals): the block decode's divisors -- unit_size, unit_hpx, nmb, h, hk_ratio -- as multiply-shift reciprocals (the LAST member: the kernel reads it by offset)
+  W64Rc rc;
 };
+// fa_fwd_w64: dense-grid block vb -> (batch, head, query block).  This is xcd_interleave (fa_device.h) followed by the split of the work index, spelled out with
+// every division by a launch constant done through its reciprocal: three scalar instructions each instead of a few dozen, in per-block code that is paid for by the
+// instruction byte.  mirror = the walk's odd rounds under a right-bounded mask: same unit, item unit_size - 1 - item.  false for the padding workgroups of a partially
+// filled last round.  Host-callable so that tests/test_w64_decode_cpu.py can walk it against the divisions.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool fwd_w64_decode(const FwdK& p, const W64Rc& rc, int32_t vb, bool mirror, int32_t& b, int32_t& h, int32_t& m_block) {
+  const int32_t xcd = vb & 7, slot = vb >> 3;
+  const int32_t j = fastdiv(slot, rc_get(rc, RC_UNIT));
+  int32_t item = slot - j * p.unit_size;
+  if (mirror) item = p.unit_size - 1 - item;
+  int32_t unit = xcd + 8 * j;
+  if (p.unit_hpx > 0) {
+    const int32_t bb = fastdiv(j, rc_get(rc, RC_HPX));
+    unit = bb * (8 * p.unit_hpx) + xcd * p.unit_hpx + (j - bb * p.unit_hpx);
+  }
+  if (unit >= p.n_units) return false;
+  const int32_t w = unit * p.unit_size + item;
+  const int32_t bh = fastdiv(w, rc_get(rc, RC_NMB));
+  const int32_t mbr = w - bh * p.nmb;
+  m_block = (p.wr >= 0) ? (p.nmb - 1 - mbr) : mbr;
+  b = fastdiv(bh, rc_get(rc, RC_H));
+  h = bh - b * p.h;
+  return true;
+}
+inline void fwd_w64_reciprocals(FwdK& k) {
+  const int32_t d[5] = {k.unit_size, k.unit_hpx, k.nmb, k.h, k.hk_ratio};
+  k.rc.shifts = 0u;
+  for (int i = 0; i < 5; ++i) { const FastDiv f = fastdiv_make(d[i]); k.rc.mul[i] = f.mul; k.rc.shifts |= f.shift << (6 * i); }
+}
 
 // FP8 forward (fa_fwd_fp8.hip): per-(batch, kv head) fp32 descale factors, nullptr = 1.0; element (b, hk) at ptr[b * bs + hk * hs]
 struct Fp8K {
