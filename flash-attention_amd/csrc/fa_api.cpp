@@ -6,6 +6,7 @@
 // mha_varlen_fwd :538-788, mha_bwd :800-1008, mha_varlen_bwd :1010-1241, set_params_fprop :44-177
 // (window/causal normalisation :155-162 and :422-427).  No ATen here: buffers are caller-owned.
 #include <hip/hip_runtime.h>
+#include <dlfcn.h>
 
 #include <algorithm>
 #include <atomic>
@@ -63,6 +64,7 @@ const fa::Knobs* read_knobs() {
   k->pack_gqa = env_int("FA_PACK_GQA", 1);
   k->fp8_kv_ring = env_int("FA_FP8_KV_RING", 4);
   if (k->fp8_kv_ring < 2 || k->fp8_kv_ring > 4) k->fp8_kv_ring = 4;
+  k->launch_log = env_int("FA_DEBUG_LAUNCH_LOG", 0);
   if (k->strict) k->rescale_thr = 0.f;
   return k;
 }
@@ -82,6 +84,24 @@ LastSchedule& last_schedule() {
   thread_local LastSchedule ls{};
   return ls;
 }
+// Launch log (fa_launch.h): host pointers of the kernels this thread's last C ABI call enqueued.  A call launches a handful of kernels (the 5-contraction backward
+// one per chunk); past the capacity only the count goes on and fa_launch_log says so.
+namespace {
+constexpr int kLaunchLogCap = 256;
+struct LaunchLog { int n; const void* kern[kLaunchLogCap]; };
+LaunchLog& launch_log() {
+  thread_local LaunchLog l{};
+  return l;
+}
+}  // namespace
+void launch_log_push(const void* kern) {
+  LaunchLog& l = launch_log();
+  if (l.n < kLaunchLogCap) l.kern[l.n] = kern;
+  ++l.n;
+}
+void launch_log_clear() { launch_log().n = 0; }
+int launch_log_count() { return launch_log().n; }
+const void* launch_log_at(int i) { return (i >= 0 && i < launch_log().n && i < kLaunchLogCap) ? launch_log().kern[i] : nullptr; }
 }  // namespace fa
 namespace {
 
@@ -339,6 +359,7 @@ int resolve_fwd_features(const FaFwdParams* a, int nw, int wr, int n_splits, int
 }
 
 int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false) {
+  fa::launch_log_clear();
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true, a->d_v)) return rc;
@@ -780,6 +801,7 @@ int launch_dkdv_any(const FaBwdParams* a, const fa::BwdK& k_in, int bf, int dk_,
 }
 
 int do_bwd(const FaBwdParams* a, void* stream, bool varlen) {
+  fa::launch_log_clear();
   fa::BwdK k;
   if (int rc = fill_bwd(a, varlen, k)) return rc;
   hipStream_t s = (hipStream_t)stream;
@@ -906,6 +928,7 @@ int do_bwd(const FaBwdParams* a, void* stream, bool varlen) {
 // FP8 forward (fa_fwd_fp8.hip): e4m3 q / k / v, bf16 o.  Plain attention under causal / window masks, head dims 64 / 128, fixed-length
 // and packed batches; every other feature is refused here, before any launch.
 int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool varlen) {
+  fa::launch_log_clear();
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   const char* fn = varlen ? "fa_varlen_fwd_fp8" : "fa_fwd_fp8";
@@ -995,6 +1018,7 @@ int do_fwd_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream, bool va
 // FP8 forward against an fp8 KV cache (fa_fwd_fp8_kv.hip): the decode side of do_fwd_fp8.  cache_seqlens (seqused_k + seqused_k_add), cache_batch_idx, a paged
 // cache, causal / window masks, head packing and split keys as fa_fwd_kvcache; everything else is refused here, before any launch.
 int do_fwd_kvcache_fp8(const FaFwdParams* a, const FaFp8Params* f, void* stream) {
+  fa::launch_log_clear();
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   const char* fn = "fa_fwd_kvcache_fp8";
@@ -1108,6 +1132,26 @@ int fa_last_schedule(int32_t* out, int n) {
   return FA_SCHEDULE_FIELDS;
 }
 const char* fa_last_kernel_name(void) { return fa::last_schedule().name; }
+// The kernels of the calling thread's last launching call, as the symbol names of the code objects, one per line.  A kernel's host-side handle carries the
+// device symbol's name in the library's dynamic symbol table (dladdr: host only, works before any device is touched); a handle that is not exported is asked of
+// the runtime (hipKernelNameRefByPtr); "?" if neither knows it.
+int fa_launch_log(char* buf, int n) {
+  const int count = fa::launch_log_count();
+  int used = 0;   // bytes of text so far, without the terminator
+  if (buf && n > 0) buf[0] = 0;
+  for (int i = 0; i < count; ++i) {
+    const void* kern = fa::launch_log_at(i);
+    const char* name = nullptr;
+    Dl_info info;
+    if (kern && dladdr(kern, &info) != 0 && info.dli_sname && info.dli_saddr == kern) name = info.dli_sname;
+    if (kern && !name) name = hipKernelNameRefByPtr(kern, nullptr);
+    if (!name || !*name) name = kern ? "?" : "?overflow";
+    const int len = (int)strlen(name);
+    if (buf && used + len + 1 < n) { memcpy(buf + used, name, len); buf[used + len] = '\n'; buf[used + len + 1] = 0; }
+    used += len + 1;
+  }
+  return used + 1;
+}
 // (the schedule resolution of do_fwd for the entry points without a KV cache: same heuristic, same feature resolution, no split keys)
 int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
@@ -1154,6 +1198,7 @@ int fa_varlen_fwd(const FaFwdParams* params, void* stream) { return do_fwd(param
 int fa_fwd_kvcache(const FaFwdParams* params, void* stream) { return do_fwd(params, stream, false, true); }
 
 int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
+  fa::launch_log_clear();
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (!a->knew || !a->vnew || !a->kcache || !a->vcache) return fail(FA_ERR_INVALID_ARGUMENT, "knew, vnew, kcache and vcache must be non-NULL");
@@ -1193,6 +1238,7 @@ int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
 }
 
 int fa_rotary(const FaRotaryParams* a, void* stream) {
+  fa::launch_log_clear();
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   g_err[0] = 0;
   if (!a->x || !a->y || !a->cos || !a->sin) return fail(FA_ERR_INVALID_ARGUMENT, "x, y, cos and sin must be non-NULL");
@@ -1214,6 +1260,7 @@ int fa_rotary(const FaRotaryParams* a, void* stream) {
 }
 
 int fa_set_rng_state(uint64_t seed, uint64_t offset, uint64_t* rng_state, void* stream) {
+  fa::launch_log_clear();
   g_err[0] = 0;
   if (!rng_state) return fail(FA_ERR_INVALID_ARGUMENT, "rng_state is NULL");
   if (fa::launch_set_rng(seed, offset, rng_state, (hipStream_t)stream) != 0)

@@ -885,7 +885,7 @@ static int launch_fused_t(const BwdK& p, hipStream_t stream) {
   static const int n_cu = [] { int dev = 0, n = 0; return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256; }();
   BwdK q = p;
   q.fuse_total = (int)total;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(total < n_cu ? total : n_cu)), dim3(512), smem, stream, q);   // one workgroup per CU (the LDS footprint admits no second one)
+  FA_LAUNCH(kern, dim3((unsigned)(total < n_cu ? total : n_cu)), dim3(512), smem, stream, q);   // one workgroup per CU (the LDS footprint admits no second one)
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1216,7 +1216,7 @@ template <typename E, int D, int DV, int DVV = DV>
 static int launch_delta_t(const BwdK& p, hipStream_t stream) {
   constexpr int ROWS = 256 / (D / 8);
   dim3 grid((p.sq + ROWS - 1) / ROWS, p.h, p.b);
-  hipLaunchKernelGGL((fa_bwd_delta_kernel<E, D, DV, DVV>), grid, dim3(256), 0, stream, p);
+  FA_LAUNCH((fa_bwd_delta_kernel<E, D, DV, DVV>), grid, dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1228,7 +1228,7 @@ static int launch_dkdv_a(const BwdK& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_mask{0};
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;   // (operand reads address LDS by byte offset: the dynamic segment starts at 0)
   const long long total = p.k_list ? (long long)p.k_bound * p.h_k : units_grid(p.k_units, p.k_unit_size);
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NWK * 64), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(NWK * 64), smem, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1263,7 +1263,7 @@ static int launch_dq_nw(const BwdK& p, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_mask{0};
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;   // (operand reads address LDS by byte offset: the dynamic segment starts at 0)
   const long long total = p.q_list ? (long long)p.q_bound * p.h : units_grid(p.q_units, p.q_unit_size);
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 template <typename E, int D, int DV, int FEAT>
@@ -1310,8 +1310,8 @@ int launch_bwd_gsum(const void* src, void* dst, int dtype_bf16, int b, int sk, i
   const long long total = (long long)b * sk * h_k * (d / 8);
   if (total <= 0) return 0;
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (dtype_bf16) hipLaunchKernelGGL(fa_bwd_gsum_kernel<__bf16>, grid, dim3(256), 0, stream, (const __bf16*)src, (__bf16*)dst, total, sk, h_k, gs, d / 8, dst_bs, dst_rs, dst_hs);
-  else hipLaunchKernelGGL(fa_bwd_gsum_kernel<_Float16>, grid, dim3(256), 0, stream, (const _Float16*)src, (_Float16*)dst, total, sk, h_k, gs, d / 8, dst_bs, dst_rs, dst_hs);
+  if (dtype_bf16) FA_LAUNCH(fa_bwd_gsum_kernel<__bf16>, grid, dim3(256), 0, stream, (const __bf16*)src, (__bf16*)dst, total, sk, h_k, gs, d / 8, dst_bs, dst_rs, dst_hs);
+  else FA_LAUNCH(fa_bwd_gsum_kernel<_Float16>, grid, dim3(256), 0, stream, (const _Float16*)src, (_Float16*)dst, total, sk, h_k, gs, d / 8, dst_bs, dst_rs, dst_hs);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 int launch_bwd_dkdv(const BwdK& p, int dtype_bf16, int d, hipStream_t stream) { FA_BWD_DISPATCH(launch_dkdv_t) }

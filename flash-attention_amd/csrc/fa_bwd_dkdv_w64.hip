@@ -944,7 +944,7 @@ static int launch_c5_t(const BwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, 160 * 1024, true) != 0) return -1;
   const long long total = (long long)p.c5_np + p.c5_nc;
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -973,7 +973,7 @@ static int launch_dkdv_w64_f(const BwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, 160 * 1024, true) != 0) return -1;
   const long long total = p.k_list ? (long long)p.k_bound * p.h_k : units_grid(p.k_units, p.k_unit_size);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 template <typename E, int D>

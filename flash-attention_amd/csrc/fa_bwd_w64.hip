@@ -730,7 +730,7 @@ static int launch_bwd_dq_w64_f(const BwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;
   const long long total = p.q_list ? (long long)p.q_bound * p.h : units_grid(p.q_units, p.q_unit_size);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(256), smem, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -634,13 +634,13 @@ __global__ void __launch_bounds__(256) fa_splitkv_combine_kernel(const FwdK p) {
 template <typename E>
 static int launch_combine_e(const FwdK& p, int d, dim3 grid, dim3 block, hipStream_t stream) {
   switch (d) {
-    case 512: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 512, 512>), grid, block, 0, stream, p); break;   // fa_fwd_mla_kernel's partials (value width)
-    case 256: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 256, 256>), grid, block, 0, stream, p); break;
-    case 192: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 256, 192>), grid, block, 0, stream, p); break;
-    case 128: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 128, 128>), grid, block, 0, stream, p); break;
-    case 96: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 128, 96>), grid, block, 0, stream, p); break;
-    case 64: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 64, 64>), grid, block, 0, stream, p); break;
-    case 32: hipLaunchKernelGGL((fa_splitkv_combine_kernel<E, 64, 32>), grid, block, 0, stream, p); break;
+    case 512: FA_LAUNCH((fa_splitkv_combine_kernel<E, 512, 512>), grid, block, 0, stream, p); break;   // fa_fwd_mla_kernel's partials (value width)
+    case 256: FA_LAUNCH((fa_splitkv_combine_kernel<E, 256, 256>), grid, block, 0, stream, p); break;
+    case 192: FA_LAUNCH((fa_splitkv_combine_kernel<E, 256, 192>), grid, block, 0, stream, p); break;
+    case 128: FA_LAUNCH((fa_splitkv_combine_kernel<E, 128, 128>), grid, block, 0, stream, p); break;
+    case 96: FA_LAUNCH((fa_splitkv_combine_kernel<E, 128, 96>), grid, block, 0, stream, p); break;
+    case 64: FA_LAUNCH((fa_splitkv_combine_kernel<E, 64, 64>), grid, block, 0, stream, p); break;
+    case 32: FA_LAUNCH((fa_splitkv_combine_kernel<E, 64, 32>), grid, block, 0, stream, p); break;
     default: return -2;
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -710,8 +710,8 @@ int launch_rotary(const RotaryK& p, int dtype_bf16, hipStream_t stream) {
   const int64_t total = (int64_t)p.b * p.s * p.h * (rc / 2 + (cpr - rc));
   if (total <= 0) return 0;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
-  if (dtype_bf16) hipLaunchKernelGGL(fa_rotary_kernel<__bf16>, grid, block, 0, stream, p);
-  else hipLaunchKernelGGL(fa_rotary_kernel<_Float16>, grid, block, 0, stream, p);
+  if (dtype_bf16) FA_LAUNCH(fa_rotary_kernel<__bf16>, grid, block, 0, stream, p);
+  else FA_LAUNCH(fa_rotary_kernel<_Float16>, grid, block, 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -798,7 +798,7 @@ __global__ void __launch_bounds__(1024) fa_varlen_schedule_kernel(const SchedK p
   }
 }
 int launch_varlen_schedule(const SchedK& p, hipStream_t stream) {
-  hipLaunchKernelGGL(fa_varlen_schedule_kernel, dim3(1), dim3(1024), 0, stream, p);
+  FA_LAUNCH(fa_varlen_schedule_kernel, dim3(1), dim3(1024), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -807,7 +807,7 @@ __global__ void fa_set_rng_kernel(uint64_t seed, uint64_t offset, uint64_t* dst)
   dst[1] = offset;
 }
 int launch_set_rng(uint64_t seed, uint64_t offset, uint64_t* dst, hipStream_t stream) {
-  hipLaunchKernelGGL(fa_set_rng_kernel, dim3(1), dim3(1), 0, stream, seed, offset, dst);
+  FA_LAUNCH(fa_set_rng_kernel, dim3(1), dim3(1), 0, stream, seed, offset, dst);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -845,7 +845,7 @@ int launch_kv_append(const KvAppendK& p, hipStream_t stream) {
   if (p.b <= 0 || p.s_new <= 0) return 0;
   const int per_b = p.s_new * p.h_k * (p.d / 8);
   dim3 grid((unsigned)std::min(256, (per_b + 255) / 256), (unsigned)p.b);
-  hipLaunchKernelGGL(fa_kv_append_kernel, grid, dim3(256), 0, stream, p);
+  FA_LAUNCH(fa_kv_append_kernel, grid, dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -859,7 +859,7 @@ static int launch_fwd_t(const FwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem) != 0) return -1;
   const long long total = units_grid(p.n_units, p.unit_size);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
   if (hipGetLastError() != hipSuccess) return -1;
   LastSchedule& ls = last_schedule();
   ls.fwd_kernel = 1; ls.fwd_nw = PP ? 16 : NW; ls.fwd_feat = FEAT; ls.fwd_splits = p.n_splits; ls.fwd_list = p.work_list != nullptr; ls.d = DV;

@@ -319,7 +319,7 @@ static int launch_fwd_dv_e(const FwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem) != 0) return -1;
   const long long total = p.work_list ? (long long)p.work_bound * p.h : units_grid(p.n_units, p.unit_size);  // (the list names every non-empty block)
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
   if (hipGetLastError() != hipSuccess) return -1;
   LastSchedule& ls = last_schedule();
   ls.fwd_kernel = 6; ls.fwd_nw = NW; ls.fwd_feat = FEAT_NONE; ls.fwd_splits = 1; ls.fwd_list = p.work_list != nullptr; ls.d = DQK; ls.dv = DV;

@@ -152,7 +152,7 @@ static int launch_fwd_fp8_t(const FwdK& p, const Fp8K& f8, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem, true) != 0) return -1;
   const long long total = p.work_list ? (long long)p.work_bound * p.h : units_grid(p.n_units, p.unit_size);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, stream, p, f8);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(256), smem, stream, p, f8);
   if (hipGetLastError() != hipSuccess) return -1;
   LastSchedule& ls = last_schedule();
   ls.fwd_kernel = 4; ls.fwd_nw = 4; ls.fwd_feat = 0; ls.fwd_splits = 1; ls.fwd_list = p.work_list != nullptr; ls.d = D;

@@ -385,7 +385,7 @@ static int launch_fwd_mla_e(const FwdK& p, hipStream_t stream) {
   if (ensure_dyn_lds(attr_mask, (const void*)kern, smem) != 0) return -1;
   const long long total = units_grid(p.n_units, p.unit_size);
   if (total <= 0) return 0;
-  hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
+  FA_LAUNCH(kern, dim3((unsigned)total), dim3(NW * 64), smem, stream, p);
   if (hipGetLastError() != hipSuccess) return -1;
   LastSchedule& ls = last_schedule();
   ls.fwd_kernel = 7; ls.fwd_nw = NW; ls.fwd_feat = FEAT_NONE; ls.fwd_splits = p.n_splits; ls.fwd_list = 0; ls.d = DQK; ls.dv = DV; ls.fwd_pack = p.pack_g;

@@ -1121,7 +1121,7 @@ static int launch_fwd_w64_t(const FwdK& p, hipStream_t stream) {
     grid = cus / 8 * 8;
     pp.persist_total = (int)total;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), smem, stream, pp);
+  FA_LAUNCH(kern, dim3((unsigned)grid), dim3(256), smem, stream, pp);
   if (hipGetLastError() != hipSuccess) return -1;
   LastSchedule& ls = last_schedule();
   ls.fwd_kernel = 3; ls.fwd_nw = 4; ls.fwd_feat = FEAT; ls.fwd_splits = 1; ls.fwd_list = p.work_list != nullptr; ls.d = D;

@@ -32,6 +32,7 @@ struct Knobs {
                        // default 0 = every score scaled in fp32 (FEAT_EXACT)
   int bwd_fuse_delta;  // FA_BWD_FUSE_DELTA=0: always run the delta pre-pass (default 1: the 64-rows-per-wave dQ kernel computes softmax_d of its rows itself and runs first)
   int fp8_kv_ring;     // FA_FP8_KV_RING: K / V staging slots of the fp8 KV-cache forward (fa_fwd_fp8_kv.hip; the LDS-DMA runs one tile less ahead): 2, 3 or 4 (default 4)
+  int launch_log;      // FA_DEBUG_LAUNCH_LOG=1: every launch notes its kernel in a per-thread list (fa_launch_log in the C ABI; tests); default 0 = nothing is recorded
   int strict;          // FA_STRICT=1: the reference's numerics contract -- rescale on any growth of a row maximum (threshold 0) and
                        // softmax_scale applied in fp32 to every score (never the bf16 pre-scaled Q of the 64-rows-per-wave kernel)
 };
@@ -52,6 +53,22 @@ struct LastSchedule {
   char name[96];
 };
 LastSchedule& last_schedule();
+
+// Launch log (FA_DEBUG_LAUNCH_LOG=1; tests/test_kernel_census_gpu.py): which __global__ instantiations the calling thread's last C ABI call enqueued, in
+// order.  Every launch of the library goes through FA_LAUNCH.  With the knob off the note is one load of the knob and one not-taken branch: nothing is stored and
+// no string is formed on the launch path (names are resolved from the host pointers only when fa_launch_log is called).  Defined in fa_api.cpp.
+void launch_log_push(const void* kern);
+void launch_log_clear();
+int launch_log_count();
+const void* launch_log_at(int i);
+template <typename K> inline void launch_log_note(K kern) {
+  if (__builtin_expect(knobs().launch_log != 0, 0)) launch_log_push(reinterpret_cast<const void*>(kern));
+}
+#define FA_LAUNCH(kern, grid, block, smem, stream, ...) \
+  do {                                                  \
+    ::fa::launch_log_note(kern);                        \
+    hipLaunchKernelGGL(kern, grid, block, smem, stream, __VA_ARGS__); \
+  } while (0)
 
 // CUs of the current device (cached per device id)
 inline int device_cu_count() {

@@ -95,7 +95,7 @@ class FaBwdParams(C.Structure):
 
 EXPORTS = (
     "fa_abi_version", "fa_sizeof_fwd_params", "fa_sizeof_bwd_params", "fa_sizeof_kvappend_params", "fa_sizeof_rotary_params",
-    "fa_last_error", "fa_rotary", "fa_knobs_reload", "fa_last_schedule", "fa_last_kernel_name", "fa_fwd_schedule_query", "fa_bwd_dq_schedule_query", "fa_bwd_plan_query",
+    "fa_last_error", "fa_rotary", "fa_knobs_reload", "fa_last_schedule", "fa_last_kernel_name", "fa_launch_log", "fa_fwd_schedule_query", "fa_bwd_dq_schedule_query", "fa_bwd_plan_query",
     "fa_fwd", "fa_varlen_fwd", "fa_fwd_kvcache", "fa_kvcache_append", "fa_set_rng_state", "fa_fwd_workspace_bytes",
     "fa_bwd_workspace_bytes", "fa_bwd", "fa_varlen_bwd", "fa_bwd_fused_status",
     "fa_sizeof_fp8_params", "fa_fwd_fp8", "fa_varlen_fwd_fp8", "fa_fwd_kvcache_fp8",
@@ -148,6 +148,8 @@ def load():
     lib.fa_last_schedule.argtypes = [C.POINTER(C.c_int32), C.c_int]
     lib.fa_last_schedule.restype = C.c_int
     lib.fa_last_kernel_name.restype = C.c_char_p
+    lib.fa_launch_log.argtypes = [C.c_char_p, C.c_int]
+    lib.fa_launch_log.restype = C.c_int
     lib.fa_fwd_schedule_query.argtypes = [C.POINTER(FaFwdParams), C.c_int]
     lib.fa_fwd_schedule_query.restype = C.c_int
     lib.fa_bwd_dq_schedule_query.argtypes = [C.POINTER(FaBwdParams)]

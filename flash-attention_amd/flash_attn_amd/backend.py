@@ -64,6 +64,19 @@ def last_schedule() -> dict:
     return d
 
 
+def launch_log() -> List[str]:
+    """Symbol names of the kernels this thread's last launching call enqueued, in launch order (C ABI fa_launch_log).  Empty unless the
+    knobs were read with FA_DEBUG_LAUNCH_LOG=1 in the environment (tests)."""
+    lib = _cabi.load()
+    n = 4096
+    while True:
+        buf = C.create_string_buffer(n)
+        need = int(lib.fa_launch_log(buf, n))
+        if need <= n:
+            return buf.value.decode().split("\n")[:-1] if need > 1 else []
+        n = need
+
+
 def _dtype_code(t: torch.Tensor) -> int:
     if t.dtype == torch.bfloat16:
         return _cabi.FA_DTYPE_BF16

@@ -253,6 +253,11 @@ void fa_knobs_reload(void);
 int fa_last_schedule(int32_t* out, int n);
 /* Name of the forward kernel instantiation of that call, e.g. "fa::fa_fwd_il_kernel<bf16,128,4,3>" ("" if none). */
 const char* fa_last_kernel_name(void);
+/* Launch log (tests; FA_DEBUG_LAUNCH_LOG=1 in the environment when the knobs are read, else nothing is recorded): the __global__ instantiations the calling
+ * thread's last launching call (fa_fwd*, fa_varlen_fwd*, fa_fwd_kvcache*, fa_bwd, fa_varlen_bwd, fa_rotary, fa_kvcache_append, fa_set_rng_state) enqueued, in launch
+ * order, as the (mangled) symbol names of the code objects, each followed by '\n'.  Writes what fits into buf[0..n) (whole lines, 0-terminated) and returns the
+ * bytes the whole text needs, terminator included (1 = empty log): call again with a larger buffer if that exceeds n. */
+int fa_launch_log(char* buf, int n);
 /* Host logic only (no launch, no pointer is dereferenced -- pointers count as flags: alibi_slopes, block_table, cu_seqlens_q, seqused_q): the forward
  * schedule fa_fwd (varlen = 0) / fa_varlen_fwd (varlen = 1) would run for these parameters, as an FA_FWD_NW code -- 64 = 64-rows-per-wave kernel,
  * 34 / 38 = software-pipelined kernel with 4 / 8 waves, 4 / 8 / 16 = lock-step kernel -- after the feature / head-dim / head-packing fallbacks; and the dQ

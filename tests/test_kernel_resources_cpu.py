@@ -4,44 +4,9 @@ vmcnt(0) -- i.e. on the LDS-DMA prefetch in flight -- and round 3 found the ALiB
 (profiles/r03_bwd_alibi_spills.txt).  The rule pinned here: no scratch in any kernel of the plain / softcap / ALiBi variants at head dims <= 128,
 none at all in the 64-rows-per-wave and pipelined kernels; the dropout combinations, the run-time-checked all-features variants and head dim 256
 may keep the few spills listed in profiles/r03_resource_usage.txt (tools/resource_usage.py prints the same table from the sources)."""
-import os
-import re
-import subprocess
-import tempfile
+from tests._kernel_census import kernel_metadata, template_ints
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "flash-attention_amd", "libfa_gfx950.so")
-LLVM = "/opt/rocm/lib/llvm/bin"
-MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FEAT_DROP = 4   # fa_device.h: FEAT bit of dropout; 7 = the run-time-checked "all" variant
-
-
-def kernel_metadata():
-    tools = [os.path.join(LLVM, t) for t in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf")]
-    if not os.path.exists(LIB) or not all(os.path.exists(t) for t in tools):
-        pytest.skip("library not built or LLVM binutils not found")
-    kernels = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        fat = os.path.join(tmp, "fat.bin")
-        subprocess.check_call([tools[0], f"--dump-section=.hip_fatbin={fat}", LIB, os.path.join(tmp, "copy.so")])
-        data = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(MAGIC), data)]   # one bundle per translation unit
-        for i, p in enumerate(starts):
-            piece, obj = os.path.join(tmp, f"b{i}.bin"), os.path.join(tmp, f"co{i}.o")
-            open(piece, "wb").write(data[p:starts[i + 1] if i + 1 < len(starts) else len(data)])
-            subprocess.check_call([tools[1], "--unbundle", "--type=o", f"--input={piece}", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={obj}"])
-            notes = subprocess.run([tools[2], "--notes", obj], capture_output=True, text=True, check=True).stdout
-            for block in notes.split("- .agpr_count:")[1:]:
-                f = {k: v for k, v in re.findall(r"\.(name|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|vgpr_count):\s+(\S+)", block)}
-                kernels[f["name"]] = {k: int(v) for k, v in f.items() if k != "name"}
-    return kernels
-
-
-def template_ints(name):
-    """Integer template arguments of an Itanium-mangled fa:: kernel name, in order."""
-    return [int(x) for x in re.findall(r"Li(\d+)E", name)]
 
 
 def test_no_scratch_in_the_hot_kernels():
