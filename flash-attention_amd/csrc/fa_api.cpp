@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/fa_gfx950.h"
 #include "fa_device.h"
@@ -303,6 +304,58 @@ int check_common(int b, int h, int h_k, int d, int dtype, float softcap, bool fo
   return FA_OK;
 }
 
+// Layout contract of the 16-bit entry points (fa_gfx950.h, "Layout contract"): every kernel moves a row in 16-byte chunks -- ld_global_16B, the
+// buffer_load_dwordx4 .. lds of the 64-per-wave kernels, 16-byte stores -- from base + (b * bs + row * rs + head * hs) * 2, so every pointer is 16-byte
+// aligned and every stride that is multiplied by a non-zero index a multiple of 8 elements.  n_batch / n_rows / n_heads are the extents the strides walk
+// (kMany where the extent is not a parameter: cache entries behind a batch index, pages, the rows of a packed batch); a dimension of one element is
+// never stepped, so its stride is neither checked nor used.  A stride of 0 (an expanded input) is a multiple of 8; an output written through it would
+// have several (b, row, head) share one address.  NULL tensors are skipped: the entry points refuse them by name, the sizing queries do not need them.
+constexpr int64_t kMany = 2;
+struct TensorLayout {
+  const char* name; const void* p;
+  int64_t bs, rs, hs;
+  int64_t n_batch, n_rows, n_heads;
+  bool output;
+};
+int check_layouts(const char* fn, std::initializer_list<TensorLayout> ts) {
+  for (const TensorLayout& t : ts) {
+    if (!t.p) continue;
+    if (((uintptr_t)t.p & 15u) != 0) return fail(FA_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned (the kernels move 16-byte chunks)", fn, t.name);
+    const struct { const char* what; int64_t stride, n; } dims[] = {{"batch", t.bs, t.n_batch}, {"row", t.rs, t.n_rows}, {"head", t.hs, t.n_heads}};
+    for (const auto& d : dims) {
+      if (d.n <= 1) continue;
+      if (d.stride % 8 != 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the %s stride of %s (%lld elements) must be a multiple of 8 elements = 16 bytes", fn, d.what, t.name, (long long)d.stride);
+      if (t.output && d.stride == 0)
+        return fail(FA_ERR_INVALID_ARGUMENT, "%s: the %s stride of the output %s must be non-zero", fn, d.what, t.name);
+    }
+  }
+  return FA_OK;
+}
+// fa_fwd / fa_varlen_fwd / fa_fwd_kvcache and the queries that mirror them (dtype fp16 / bf16; the MLA pair and the fp8 entry points have checks of their own)
+// (writes = false: a query, which enqueues nothing -- the rule on output strides belongs to the launching calls)
+int check_fwd_layout(const char* fn, const FaFwdParams* a, bool varlen, bool kvcache, bool writes = true) {
+  const bool packed_k = varlen && !a->block_table;
+  const int64_t nb = varlen ? 1 : a->b, rows_q = varlen ? a->total_q : a->seqlen_q;
+  const int64_t nb_k = packed_k ? 1 : (kvcache || a->block_table) ? kMany : a->b;
+  const int64_t rows_k = packed_k ? kMany : a->block_table ? a->page_block_size : a->seqlen_k;
+  return check_layouts(fn, {{"q", a->q, a->q_batch_stride, a->q_row_stride, a->q_head_stride, nb, rows_q, a->h, false},
+                            {"k", a->k, a->k_batch_stride, a->k_row_stride, a->k_head_stride, nb_k, rows_k, a->h_k, false},
+                            {"v", a->v, a->v_batch_stride, a->v_row_stride, a->v_head_stride, nb_k, rows_k, a->h_k, false},
+                            {"o", a->o, a->o_batch_stride, a->o_row_stride, a->o_head_stride, nb, rows_q, a->h, writes}});
+}
+int check_bwd_layout(const char* fn, const FaBwdParams* a, bool varlen, bool writes = true) {
+  const int64_t nb = varlen ? 1 : a->b, rq = varlen ? a->total_q : a->seqlen_q, rk = varlen ? (a->total_k > 0 ? a->total_k : kMany) : a->seqlen_k;
+  return check_layouts(fn, {{"dout", a->dout, a->do_batch_stride, a->do_row_stride, a->do_head_stride, nb, rq, a->h, false},
+                            {"q", a->q, a->q_batch_stride, a->q_row_stride, a->q_head_stride, nb, rq, a->h, false},
+                            {"k", a->k, a->k_batch_stride, a->k_row_stride, a->k_head_stride, nb, rk, a->h_k, false},
+                            {"v", a->v, a->v_batch_stride, a->v_row_stride, a->v_head_stride, nb, rk, a->h_k, false},
+                            {"o", a->o, a->o_batch_stride, a->o_row_stride, a->o_head_stride, nb, rq, a->h, false},
+                            {"dq", a->dq, a->dq_batch_stride, a->dq_row_stride, a->dq_head_stride, nb, rq, a->h, writes},
+                            {"dk", a->dk, a->dk_batch_stride, a->dk_row_stride, a->dk_head_stride, nb, rk, a->h_k, writes},
+                            {"dv", a->dv, a->dv_batch_stride, a->dv_row_stride, a->dv_head_stride, nb, rk, a->h_k, writes}});
+}
+
 // A v / o head dim of its own (FaFwdParams::d_v / FaBwdParams::d_v; 0 = d).  One pair is built: q / k 192, v / o 128 (fa_fwd_dv.hip; the backward runs the
 // 256-pitch kernels of head dim 192 with a value width of 128, fa_bwd.hip).  Everything else about such a call is refused here, before anything touches the
 // device, with a message that names both head dims or the argument.
@@ -401,6 +454,7 @@ int do_fwd(const FaFwdParams* a, void* stream, bool varlen, bool kvcache = false
   if (kvcache && a->p_dropout > 0.f) return fail(FA_ERR_INVALID_ARGUMENT, "fa_fwd_kvcache is an inference path: p_dropout must be 0");
   if (a->randval && !(a->p_dropout > 0.f)) return fail(FA_ERR_INVALID_ARGUMENT, "return_softmax is only supported when p_dropout > 0.0");
   if (a->num_splits > 1 && !kvcache) return fail(FA_ERR_INVALID_ARGUMENT, "num_splits > 1 is not supported");
+  if (!mla) if (int rc = check_fwd_layout(kvcache ? "fa_fwd_kvcache" : varlen ? "fa_varlen_fwd" : "fa_fwd", a, varlen, kvcache)) return rc;
   if (a->seqlen_q == 0 || a->total_q == 0) return FA_OK;  // nothing to write
 
   fa::FwdK k{};
@@ -618,6 +672,7 @@ int fill_bwd(const FaBwdParams* a, bool varlen, fa::BwdK& k) {
   k.scale_log2 = a->softmax_scale * 1.4426950408889634f;
   k.softcap = a->softcap;
   if (int rc = check_dropout(a->p_dropout, a->rng_state)) return rc;
+  if (int rc = check_bwd_layout(varlen ? "fa_varlen_bwd" : "fa_bwd", a, varlen)) return rc;
   fill_dropout(k, a->p_dropout, a->rng_state, a->seqlen_k);
   k.dq_nw = bwd_dq_schedule(a);
   if (!head_dim_native(a->d)) k.d_chunks = a->d / 8;   // run-time column bound of the next built size's kernels
@@ -1158,6 +1213,7 @@ int fa_fwd_schedule_query(const FaFwdParams* a, int varlen) {
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, true, a->d_v)) return rc;
   if (int rc = check_value_dim("fa_fwd_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, a->randval, a->block_table, a->leftpad_k,
                                a->cache_batch_idx || a->seqused_k_add || a->num_splits > 1, false)) return rc;   // (the MLA decode pair too: fa_fwd_kvcache only)
+  if (int rc = check_fwd_layout("fa_fwd_schedule_query", a, varlen != 0, false, false)) return rc;
   if (own_value_dim(a->d, a->d_v)) return 4;   // fa_fwd_dv_kernel: 4 waves x 32 rows
   int causal = a->is_causal, wl = a->window_left, wr = a->window_right;
   normalize_window(a->seqlen_q, a->seqlen_k, a->alibi_slopes != nullptr, causal, wl, wr);
@@ -1174,12 +1230,14 @@ int fa_bwd_dq_schedule_query(const FaBwdParams* a) {
   if (!a) return fail(FA_ERR_INVALID_ARGUMENT, "params is NULL");
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap, false, a->d_v)) return rc;
   if (int rc = check_value_dim("fa_bwd_dq_schedule_query", a->d, a->d_v, a->p_dropout, a->softcap, a->alibi_slopes, nullptr, nullptr, nullptr, false, false)) return rc;
+  if (int rc = check_bwd_layout("fa_bwd_dq_schedule_query", a, a->cu_seqlens_q != nullptr, false)) return rc;
   return bwd_dq_schedule(a);
 }
 
 int fa_bwd_plan_query(const FaBwdParams* a, int32_t* out, int n) {
   if (!a || !out) return fail(FA_ERR_INVALID_ARGUMENT, "params / out is NULL");
   if (int rc = check_common(a->b, a->h, a->h_k, a->d, a->dtype, a->softcap)) return rc;
+  if (int rc = check_bwd_layout("fa_bwd_plan_query", a, a->cu_seqlens_q != nullptr, false)) return rc;
   int32_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   C5Plan pl;
   if (!a->cu_seqlens_q && bwd_c5_plan(a, pl)) {
@@ -1216,6 +1274,11 @@ int fa_kvcache_append(const FaKvAppendParams* a, void* stream) {
     for (int64_t st : strides)
       if (st % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "fa_kvcache_append: e4m3 strides must be multiples of 16 bytes");
   }
+  if (!fp8)
+    if (int rc = check_layouts("fa_kvcache_append", {{"knew", a->knew, a->knew_batch_stride, a->knew_row_stride, a->knew_head_stride, a->b, a->seqlen_new, a->h_k, false},
+                                                     {"vnew", a->vnew, a->vnew_batch_stride, a->vnew_row_stride, a->vnew_head_stride, a->b, a->seqlen_new, a->h_k, false},
+                                                     {"kcache", a->kcache, a->kcache_batch_stride, a->kcache_row_stride, a->kcache_head_stride, kMany, kMany, a->h_k, true},
+                                                     {"vcache", a->vcache, a->vcache_batch_stride, a->vcache_row_stride, a->vcache_head_stride, kMany, kMany, a->h_k, true}})) return rc;
   fa::KvAppendK k{};
   k.knew = a->knew; k.vnew = a->vnew; k.kcache = a->kcache; k.vcache = a->vcache;
   k.kn_bs = a->knew_batch_stride; k.kn_rs = a->knew_row_stride; k.kn_hs = a->knew_head_stride;
@@ -1248,6 +1311,8 @@ int fa_rotary(const FaRotaryParams* a, void* stream) {
   if (a->rotary_dim <= 0 || a->rotary_dim > a->d) return fail(FA_ERR_INVALID_ARGUMENT, "rotary_dim must be <= headdim");
   if (a->rotary_dim % 16 != 0) return fail(FA_ERR_INVALID_ARGUMENT, "Only rotary dimensions divisible by 16 are currently supported");
   if (a->seqlen_ro <= 0) return fail(FA_ERR_INVALID_ARGUMENT, "cos/sin must have at least one row");
+  if (int rc = check_layouts("fa_rotary", {{"x", a->x, a->x_batch_stride, a->x_row_stride, a->x_head_stride, a->b, a->s, a->h, false},
+                                           {"y", a->y, a->y_batch_stride, a->y_row_stride, a->y_head_stride, a->b, a->s, a->h, true}})) return rc;
   fa::RotaryK k{};
   k.x = a->x; k.y = a->y; k.cos = a->cos; k.sin = a->sin; k.offsets = a->seqlen_offsets;
   k.x_bs = a->x_batch_stride; k.x_rs = a->x_row_stride; k.x_hs = a->x_head_stride;
@@ -1270,6 +1335,9 @@ int fa_set_rng_state(uint64_t seed, uint64_t offset, uint64_t* rng_state, void* 
 
 int64_t fa_fwd_workspace_bytes(const FaFwdParams* params) {
   if (!params) return 0;
+  // (a layout the launching call refuses gets no workspace: the refusal, with its message, comes from that call)
+  if (params->dtype != FA_DTYPE_FP8_E4M3 && !mla_pair(params->d, params->d_v) &&
+      check_fwd_layout("fa_fwd_workspace_bytes", params, params->cu_seqlens_q != nullptr, !params->cu_seqlens_q, false) != FA_OK) return 0;
   if (params->cu_seqlens_q && params->dtype == FA_DTYPE_FP8_E4M3)  // fa_varlen_fwd_fp8: 128-row blocks
     return (varlen_list_entries(params, 128) > 0) ? (varlen_list_entries(params, 128) + 1) * 8 : 0;
   if (params->cu_seqlens_q && own_value_dim(params->d, params->d_v)) {  // fa_fwd_dv_kernel: 128-row blocks
@@ -1290,6 +1358,7 @@ int64_t fa_fwd_workspace_bytes(const FaFwdParams* params) {
 int64_t fa_bwd_workspace_bytes(const FaBwdParams* params) {
   // no fp32 dq accumulator; an uneven packed batch gets work lists, a fixed-length batch the dS workspace of the 5-contraction path
   if (!params) return 0;
+  if (check_bwd_layout("fa_bwd_workspace_bytes", params, params->cu_seqlens_q != nullptr, false) != FA_OK) return 0;   // (as fa_fwd_workspace_bytes)
   int64_t qe, ke;
   bwd_list_entries(params, qe, ke);
   if (const int64_t fz = bwd_fused_ds_bytes(params); fz > 0) return fz + bwd_fused_sync_bytes(params);

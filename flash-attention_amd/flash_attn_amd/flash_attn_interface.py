@@ -587,13 +587,14 @@ def flash_attn_varlen_qkvpacked_func(qkv, cu_seqlens, max_seqlen, dropout_p=0.0,
 def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None, rotary_sin=None, cache_seqlens=None,
                             cache_batch_idx=None, cache_leftpad=None, block_table=None, softmax_scale=None, causal=False,
                             window_size=(-1, -1), softcap=0.0, rotary_interleaved=True, alibi_slopes=None, num_splits=0,
-                            return_softmax_lse=False, *, q_descale=None, k_descale=None, v_descale=None):
+                            return_softmax_lse=False, *, q_descale=None, k_descale=None, v_descale=None, out=None):
     """Inference attention against a KV cache (reference :1485-1627).  If k / v are given they are written into the
     cache in place at rows ``cache_seqlens[b] ..`` before attending; ``cache_seqlens`` may be an int or an int32
     tensor (batch,); ``cache_batch_idx`` selects cache rows; ``block_table`` selects pages of a paged cache
     (num_blocks, page, Hk, D); ``rotary_cos/sin`` (seqlen_ro, rotary_dim/2) rotate the new keys at positions
     cache_seqlens + i and the queries likewise (all at cache_seqlens unless causal / local); ``cache_leftpad`` gives the
-    first valid cache row of each entry.  No backward.
+    first valid cache row of each entry.  ``out`` (optional, shaped and typed like the result, any 16-byte-aligned strided view with a contiguous
+    last dimension) receives the result in place.  No backward.
     float8_e4m3fn q / caches / new k, v (FA3's fp8 KV cache): optional fp32 (B, Hk) ``q_descale`` / ``k_descale`` / ``v_descale`` indexed by the
     batch entry of q, bf16 out, head dims 64 / 128; new keys / values are appended as bytes (quantise them with the cache's scale); rotary,
     ``cache_leftpad``, ALiBi and softcap are refused.
@@ -629,12 +630,12 @@ def flash_attn_with_kvcache(q, k_cache, v_cache, k=None, v=None, rotary_cos=None
     if fp8:
         out, lse = flash_attn_gpu.fwd_kvcache_fp8(
             q, k_cache, v_cache, k, v, cache_seqlens, None if cache_batch_idx is None else cache_batch_idx.contiguous(),
-            None if block_table is None else _unit_stride_last(block_table), None, q_descale, k_descale, v_descale, softmax_scale, causal,
+            None if block_table is None else _unit_stride_last(block_table), out, q_descale, k_descale, v_descale, softmax_scale, causal,
             window_size[0], window_size[1], num_splits)
         return (out, lse) if return_softmax_lse else out
     out, lse = flash_attn_gpu.fwd_kvcache(
         q, k_cache, v_cache, k, v, cache_seqlens, _unit_stride_last(rotary_cos), _unit_stride_last(rotary_sin),
         None if cache_batch_idx is None else cache_batch_idx.contiguous(), cache_leftpad,
-        None if block_table is None else _unit_stride_last(block_table), alibi_slopes, None, softmax_scale, causal,
+        None if block_table is None else _unit_stride_last(block_table), alibi_slopes, out, softmax_scale, causal,
         window_size[0], window_size[1], softcap, rotary_interleaved, num_splits)
     return (out, lse) if return_softmax_lse else out

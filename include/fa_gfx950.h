@@ -21,6 +21,19 @@
  *
  * Conventions
  *   - all strides are in ELEMENTS (not bytes); the last (head-dim) stride is 1;
+ *   - Layout contract of the fp16 / bf16 entry points (fa_fwd, fa_varlen_fwd, fa_fwd_kvcache, fa_bwd, fa_varlen_bwd, the 16-bit fa_kvcache_append,
+ *     fa_rotary; the fp8 entry points and the (576, 512) pair state theirs below): the kernels move every row in 16-byte chunks, so
+ *       * every tensor pointer (q, k, v, o, dout, dq, dk, dv, knew, vnew, kcache, vcache, x, y) is 16-byte aligned;
+ *       * every batch, row and head stride is a multiple of 8 elements WHEN ITS DIMENSION HAS MORE THAN ONE ELEMENT.  The stride of a dimension of one
+ *         element (one KV head, B = 1, one query row) is never multiplied by a non-zero index: any value is accepted and none is relied upon.  Extents
+ *         that are not parameters (cache entries behind cache_batch_idx, pages, the key rows of a packed batch) count as more than one;
+ *       * a stride of 0 is accepted for inputs (a tensor expanded over the batch or the heads);
+ *       * outputs (o, dq, dk, dv, kcache, vcache of the append, y) have non-zero strides in every dimension of more than one element (the launching
+ *         calls check this; the queries, which write nothing, do not).
+ *     Within that, the tensors of one call are independent: each has its own base and its own (batch, row, head) strides (column slices of one fused
+ *     projection, transposed (B,H,S,D) / (S,B,H,D) buffers, views of a packed gradient, padded heads, every second row ...).  A violation returns
+ *     FA_ERR_INVALID_ARGUMENT with a message naming the entry point and the tensor, before anything touches the device; fa_fwd_schedule_query,
+ *     fa_bwd_dq_schedule_query and fa_bwd_plan_query return the same error, fa_fwd_workspace_bytes / fa_bwd_workspace_bytes return 0;
  *   - q (B,Sq,H,D), k/v (B,Sk,Hk,D), o like q; varlen: q (total_q,H,D), k/v (total_k,Hk,D) and
  *     batch strides are ignored; sequence b owns rows cu_seqlens[b] .. cu_seqlens[b+1]-1
  *     (reference csrc/flash_attn/src/block_info.h:12-45);
