@@ -1,6 +1,7 @@
 """Build the gfx950 attention libraries in-tree (no JIT cache, no pip install).
 
   libfa_gfx950.so      C-ABI library (include/fa_gfx950.h): HIP kernels + host validation
+  libfa_gfx950_quant.so  C-ABI library (include/fa_gfx950_quant.h): bf16 / fp16 -> e4m3 quantisation and the quantising KV-cache append
   flash_attn_2_cuda*.so  torch extension exposing the reference backend-module API
                          (fwd / varlen_fwd / bwd / varlen_bwd / fwd_kvcache) on top of the C ABI
   probe_gfx950         hardware-semantics probe (lane layouts the kernels rely on)
@@ -26,6 +27,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 LIB = os.path.join(HERE, "libfa_gfx950.so")
+QUANT_LIB = os.path.join(HERE, "libfa_gfx950_quant.so")
 PROBE = os.path.join(HERE, "probe_gfx950")
 
 
@@ -83,6 +85,23 @@ def build_lib(force=False):
     return LIB
 
 
+# (source, object, extra flags) of libfa_gfx950_quant.so: a library of its own, so that UNITS stays "the library" for the kernel census and tools/resource_usage.py.
+QUANT_UNITS = [("fa_quant.hip", "fa_quant.o", [])]
+
+
+def build_quant_lib(force=False):
+    hdr = os.path.join(ROOT, "include", "fa_gfx950_quant.h")
+    objs = []
+    for u, o, extra in QUANT_UNITS:
+        src, obj = os.path.join(CSRC, u), os.path.join(CSRC, o)
+        if force or not _newer(obj, [src, hdr]):
+            _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("FA_EXTRA_HIPCC_FLAGS", "").split() + extra + ["-c", src, "-o", obj])
+        objs.append(obj)
+    if force or not _newer(QUANT_LIB, objs):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", QUANT_LIB] + objs)
+    return QUANT_LIB
+
+
 def build_probe(force=False):
     src = os.path.join(CSRC, "probe_gfx950.hip")
     if force or not _newer(PROBE, [src]):
@@ -121,6 +140,7 @@ def main(argv=None):
     ap.add_argument("--force", action="store_true")
     a = ap.parse_args(argv)
     build_lib(a.force)
+    build_quant_lib(a.force)
     build_probe(a.force)
     if not a.no_torch_ext and os.path.exists(os.path.join(CSRC, "torch_binding.cpp")):
         build_torch_ext(a.force)

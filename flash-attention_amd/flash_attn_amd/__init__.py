@@ -11,3 +11,4 @@ from .flash_attn_interface import (  # noqa: F401
     flash_attn_varlen_qkvpacked_func,
     flash_attn_with_kvcache,
 )
+from .fp8_quant import kvcache_append_fp8, quantize_fp8  # noqa: F401
