@@ -12,3 +12,4 @@ from .flash_attn_interface import (  # noqa: F401
     flash_attn_with_kvcache,
 )
 from .fp8_quant import kvcache_append_fp8, quantize_fp8  # noqa: F401
+from .combine import flash_attn_combine, merge_attn_states  # noqa: F401
