@@ -3,6 +3,7 @@
   libfa_gfx950.so      C-ABI library (include/fa_gfx950.h): HIP kernels + host validation
   libfa_gfx950_quant.so  C-ABI library (include/fa_gfx950_quant.h): bf16 / fp16 -> e4m3 quantisation and the quantising KV-cache append
   libfa_gfx950_combine.so  C-ABI library (include/fa_gfx950_combine.h): the merge of partial attention results (out, lse)
+  libfa_gfx950_sink.so   C-ABI library (include/fa_gfx950_sink.h): learnable attention sinks as a post-pass over (out, lse), and their gradient
   flash_attn_2_cuda*.so  torch extension exposing the reference backend-module API
                          (fwd / varlen_fwd / bwd / varlen_bwd / fwd_kvcache) on top of the C ABI
   probe_gfx950         hardware-semantics probe (lane layouts the kernels rely on)
@@ -30,6 +31,7 @@ ARCH = "gfx950"
 LIB = os.path.join(HERE, "libfa_gfx950.so")
 QUANT_LIB = os.path.join(HERE, "libfa_gfx950_quant.so")
 COMBINE_LIB = os.path.join(HERE, "libfa_gfx950_combine.so")
+SINK_LIB = os.path.join(HERE, "libfa_gfx950_sink.so")
 PROBE = os.path.join(HERE, "probe_gfx950")
 
 
@@ -121,6 +123,23 @@ def build_combine_lib(force=False):
     return COMBINE_LIB
 
 
+# (source, object, extra flags) of libfa_gfx950_sink.so: a library of its own for the same reason.
+SINK_UNITS = [("fa_sink.hip", "fa_sink.o", [])]
+
+
+def build_sink_lib(force=False):
+    hdr = os.path.join(ROOT, "include", "fa_gfx950_sink.h")
+    objs = []
+    for u, o, extra in SINK_UNITS:
+        src, obj = os.path.join(CSRC, u), os.path.join(CSRC, o)
+        if force or not _newer(obj, [src, hdr]):
+            _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"] + os.environ.get("FA_EXTRA_HIPCC_FLAGS", "").split() + extra + ["-c", src, "-o", obj])
+        objs.append(obj)
+    if force or not _newer(SINK_LIB, objs):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", SINK_LIB] + objs)
+    return SINK_LIB
+
+
 def build_probe(force=False):
     src = os.path.join(CSRC, "probe_gfx950.hip")
     if force or not _newer(PROBE, [src]):
@@ -161,6 +180,7 @@ def main(argv=None):
     build_lib(a.force)
     build_quant_lib(a.force)
     build_combine_lib(a.force)
+    build_sink_lib(a.force)
     build_probe(a.force)
     if not a.no_torch_ext and os.path.exists(os.path.join(CSRC, "torch_binding.cpp")):
         build_torch_ext(a.force)

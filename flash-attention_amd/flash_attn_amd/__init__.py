@@ -13,3 +13,9 @@ from .flash_attn_interface import (  # noqa: F401
 )
 from .fp8_quant import kvcache_append_fp8, quantize_fp8  # noqa: F401
 from .combine import flash_attn_combine, merge_attn_states  # noqa: F401
+from .sink import (  # noqa: F401
+    apply_attn_sink,
+    flash_attn_sink_func,
+    flash_attn_varlen_sink_func,
+    flash_attn_with_kvcache_sink,
+)
