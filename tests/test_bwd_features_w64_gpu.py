@@ -7,10 +7,10 @@ inputs and the same forward.  dQ must
     was scaled and rounded once, the established one scales every score in fp32),
   * be bitwise reproducible; dK / dV must not move at all when only the dQ kernel changes -- except through softmax_d, which the 64-rows kernel computes itself
     in another summation order (compared with a tolerance)."""
-import math
-
 import pytest
 import torch
+
+from tests._dropout_model import threshold as dropout_threshold
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +66,7 @@ def test_dq_w64_softcap_and_dropout(be, knobs, shape, feature, dtype, d):
     sc = d ** -0.5
     torch.manual_seed(21)
     out, lse, rv, rng = be.fwd(q, k, v, None, None, p, sc, causal, wl, wr, cap, p > 0, None)
-    keep = (rv.to(torch.int32) <= math.floor(255.0 * (1.0 - p))) if p > 0 else None
+    keep = (rv.to(torch.int32) <= dropout_threshold(p)) if p > 0 else None
     bwd = lambda: be.bwd(do, q, k, v, out, lse, None, None, None, None, p, sc, causal, wl, wr, cap, False, None, rng)
     knobs.set("FA_BWD_DQ_NW", 4)
     g_old = bwd()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._dropout_model import threshold as dropout_threshold
 from tests._util import max_abs
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def be(request):
 
 
 def _keep(randval, p):
-    return randval.to(torch.int32) <= math.floor(255.0 * (1.0 - p))
+    return randval.to(torch.int32) <= dropout_threshold(p)   # formed in single precision, as the C ABI forms it
 
 
 def _visible(sq, sk, causal, window):
@@ -57,7 +58,7 @@ def test_dropout_fwd_bwd_vs_oracle(be, sq, sk, h, hk, causal, window, p, d, dtyp
     vis = _visible(sq, sk, causal, window)
     if vis.sum() * B * h > 20000:  # kept fraction of the visible pairs (reference get_dropout_fraction check)
         frac = keep[:, :, vis].mean()
-        assert abs(frac - (math.floor(255 * (1 - p)) + 1) / 256) < 0.01
+        assert abs(frac - (dropout_threshold(p) + 1) / 256) < 0.01
     o_ref, l_ref = orc.attention_fwd(q, k, v, scale, causal, window, 0.0, None, p, keep)
     tol = 2e-2 if dtype == torch.bfloat16 else 4e-3
     assert max_abs(out.float().cpu(), torch.from_numpy(o_ref)) < tol / (1 - p)

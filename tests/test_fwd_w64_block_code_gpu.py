@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._dropout_model import threshold as dropout_threshold
 from tests._util import max_abs
 from tests.test_w64_dirty_registers_gpu import dirty
 
@@ -146,7 +147,7 @@ def test_feature_variants_share_the_edited_prologue_and_epilogue(be, knobs):
     knobs.unset("FA_FWD_NW")
     assert _is_w64(s, "dropout"), s
     assert torch.equal(rng, rng8)
-    keep = (rv.to(torch.int32) <= int(np.floor(255.0 * (1.0 - p)))).cpu().numpy()
+    keep = (rv.to(torch.int32) <= dropout_threshold(p)).cpu().numpy()
     _judge(out, lse, out8, *orc.attention_fwd(q, k, v, sc, True, (-1, -1), 0.0, None, p, keep), BF16, 1.0 / (1.0 - p))
     # paged: the same keys and values in shuffled pages of 256
     page, per = 256, S // 256

@@ -9,13 +9,13 @@ the plan query saying what each run did, and dQ bit for bit the same.
 
 With FA_GOLDEN_MATRIX_RATIOS=<file> the worst err / err_pt ratio per tensor, dtype and knob setting is written there."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests._dropout_model import threshold as dropout_threshold
 from tests._util import golden_inputs, load_matrix, matrix_bound, matrix_head_dims, matrix_meta, matrix_names, max_abs
 
 pytestmark = pytest.mark.gpu
@@ -292,7 +292,7 @@ def test_dropout_under_the_split_vs_oracle(be, knobs, shape, dtype, dn):
     scale = D ** -0.5
     torch.manual_seed(3)
     out, lse, rv, rng = be.fwd(q, k, v, None, None, p, scale, causal, -1, -1, 0.0, True, None)
-    keep = (rv.to(torch.int32) <= math.floor(255.0 * (1.0 - p))).cpu().numpy()
+    keep = (rv.to(torch.int32) <= dropout_threshold(p)).cpu().numpy()
     o_ref, _ = orc.attention_fwd(q, k, v, scale, causal, (-1, -1), 0.0, None, p, keep)
     g_ref = orc.attention_bwd(do, q, k, v, None, None, scale, causal, (-1, -1), 0.0, None, p, keep)
     ref = dict(out=o_ref, dq=g_ref[0], dk=g_ref[1], dv=g_ref[2])

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests._dropout_model import threshold as dropout_threshold
 from tests._util import attention_torch, max_abs
 
 pytestmark = pytest.mark.gpu
@@ -61,7 +62,7 @@ def test_varlen_dropout_and_kvcache_at_256(be):
                                   -1, -1, 0.0, False, None, rng)
     for b, L in enumerate(lens):
         sl = slice(int(cu[b]), int(cu[b + 1]))
-        keep = (rv[:, sl, :L].to(torch.int32) <= int(255 * 0.8)).cpu().numpy()[None]
+        keep = (rv[:, sl, :L].to(torch.int32) <= dropout_threshold(0.2)).cpu().numpy()[None]
         o_ref, _ = orc.attention_fwd(q[sl][None], k[sl][None], v[sl][None], None, True, (-1, -1), 0.0, None, 0.2, keep)
         assert max_abs(out[sl].float().cpu(), torch.from_numpy(o_ref[0])) < 3e-2
         rq, rk, rvv, _ = orc.attention_bwd(do[sl][None], q[sl][None], k[sl][None], v[sl][None], None, None, None, True, (-1, -1), 0.0, None, 0.2, keep)

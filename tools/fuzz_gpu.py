@@ -100,7 +100,7 @@ def run_case(case, worst, failures, call=None, grad=None):
     if use_alibi: kw["alibi_slopes"] = alibi
     if use_cap: kw["softcap"] = cap
     if use_drop: kw["dropout_p"] = pd; kw["return_attn_probs"] = True
-    thr8 = math.floor(255 * (1 - pd))
+    thr8 = int(np.floor((np.float32(1.0) - np.float32(pd)) * np.float32(255.0)))   # single precision, as csrc/fa_api.cpp fill_dropout forms it
     al_np = None if alibi is None else alibi.cpu().numpy()
     desc = f"dtype={dtype} d={d} h={h}/{hk} B={B} sq={sq} sk={sk} mode={mode} window={window} feat={feat} varlen={varlen}"
     try:
