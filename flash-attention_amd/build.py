@@ -68,7 +68,7 @@ UNITS = [("fa_fwd.hip", "fa_fwd_bf16.o", ["-DFA_FWD_PART=1"]), ("fa_fwd.hip", "f
 
 
 def build_lib(force=False):
-    hdrs = _sources(["fa_device.h", "fa_kernel_params.h", "fa_launch.h", "fa_fp8_tile.h", "fa_fwd_block.h", "fa_w64_asm.h", "fa_fwd_w64_regs.h"]) + [os.path.join(ROOT, "include", "fa_gfx950.h")]
+    hdrs = _sources(["fa_device.h", "fa_kernel_params.h", "fa_launch.h", "fa_plan.h", "fa_fp8_tile.h", "fa_fwd_block.h", "fa_w64_asm.h", "fa_fwd_w64_regs.h"]) + [os.path.join(ROOT, "include", "fa_gfx950.h")]
     objs, cmds = [], []
     for u, o, extra in UNITS:
         src = os.path.join(CSRC, u)

@@ -346,3 +346,41 @@ def test_default_table_chunks_a_large_batch(be, knobs):
         for name, x, y, base, lo in zip(("dq", "dk", "dv"), f[:3], a[:3], r, rl):
             e, e_pair, e_pt = float((x[sl].float() - base).abs().max()), float((y[sl].float() - base).abs().max()), float((lo - base).abs().max())
             assert e <= 3 * e_pt + 1e-4 and e <= 1.5 * e_pair + 1e-4, (name, sl, e, e_pair, e_pt)
+
+
+# ---- a launch does what its query said (fa_api.cpp: both read one plan, fa_plan.h plan_bwd) ----
+def _assert_grads_within_the_reference_rule(q, k, v, do, causal, got):
+    """(the rule of test_default_table_region_takes_the_fused_launch: <= 3x the error of the same arithmetic in the input dtype, with its floor)"""
+    r, rl = ref_grads(q, k, v, do, causal, -1, -1), ref_grads(q, k, v, do, causal, -1, -1, upcast=False)
+    for name, x, base, lo in zip(("dq", "dk", "dv"), got, r, rl):
+        e, e_pt = float((x.float() - base).abs().max()), float((lo - base).abs().max())
+        assert torch.isfinite(x.float()).all() and e <= 3 * e_pt + 1e-4, (name, e, e_pt)
+
+
+@pytest.mark.parametrize("shape,causal,want", [((16, 1024, 16, 16), True, (3, 0, 4)), ((2, 1024, 32, 2), True, (0, 8, 4)), ((4, 1024, 32, 32), False, (0, 0, 64))],
+                         ids=["fused", "group_split", "dq_w64"])
+def test_bwd_launch_runs_what_its_queries_name(be, knobs, shape, causal, want):
+    """want = (fa_bwd_plan_query's word 0 -- 3: the fused launch --, its word 3 -- virtual kv heads of a split group --, fa_bwd_dq_schedule_query)"""
+    import ctypes as C
+    from flash_attn_amd import _cabi
+    B, S, H, Hk = shape
+    knobs.unset("FA_BWD_GSPLIT")   # (this module is otherwise pinned to unsplit groups, tests/conftest.py: here the default)
+    knobs.set("FA_DEBUG_LAUNCH_LOG", 1)
+    torch.manual_seed(33)
+    q = torch.randn(B, S, H, 128, device="cuda", dtype=torch.bfloat16)
+    k = torch.randn(B, S, Hk, 128, device="cuda", dtype=torch.bfloat16)
+    v, do = torch.randn_like(k), torch.randn_like(q)
+    plan = _plan_of(B, S, H, Hk, 128, causal)
+    a = _cabi.FaBwdParams()
+    a.b, a.h, a.h_k, a.d, a.dtype = B, H, Hk, 128, 1
+    a.seqlen_q, a.seqlen_k, a.total_q, a.total_k = S, S, B * S, B * S
+    a.softmax_scale, a.is_causal, a.window_left, a.window_right = 128 ** -0.5, int(causal), -1, -1
+    dq_nw = _cabi.load().fa_bwd_dq_schedule_query(C.byref(a))
+    dq, dk, dv, s, _ = run_bwd(be, q, k, v, do, causal)
+    log = be.launch_log()
+    assert (plan[0], plan[3], dq_nw) == want, (plan, dq_nw)
+    assert s["bwd_spill"] == plan[0], (plan, s)
+    assert any("fa_bwd_gsum_kernel" in n for n in log) == (plan[3] > 1), (plan, log)
+    if plan[0] == 0:
+        assert s["bwd_dq_nw"] == dq_nw, (dq_nw, s)
+    _assert_grads_within_the_reference_rule(q, k, v, do, causal, (dq, dk, dv))

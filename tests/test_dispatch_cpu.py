@@ -1,6 +1,7 @@
 """Host logic of the dispatch, on a box without a GPU: fa_fwd_schedule_query / fa_bwd_dq_schedule_query run the same heuristics the launch path uses
 (fa_api.cpp fwd_schedule_nw, pack_group, the feature / head-dim fallbacks, bwd_dq_schedule) and launch nothing.  The expectations are the measured
 choices of profiles/r03_fwd_schedules.txt and the BASELINE.json configurations."""
+import contextlib
 import ctypes as C
 import os
 
@@ -310,3 +311,183 @@ def test_gqa_group_split_plan(lib, monkeypatch):
     monkeypatch.setenv("FA_BWD_GSPLIT", "4"); lib.fa_knobs_reload()
     assert full(8, 4096, 4096, 32, 8, 128, is_causal=1)[3] == 4                    # forced (tests): up to the knob, never past the group
     monkeypatch.delenv("FA_BWD_GSPLIT"); lib.fa_knobs_reload()
+
+
+# ---- the dispatch table: every query of the host dispatch over a fixed grid, pinned to tests/golden/dispatch_table.txt ----
+# The table is recorded with this generator from a library built at the commit BEFORE a change of the dispatch (python tests/test_dispatch_cpu.py --record, with
+# FA_GFX950_LIB naming that library), never from the code under test: a refactor must reproduce it, a change of a heuristic must change it on purpose.
+# One line per (side, knob set, head dims, feature) slice: the slice's case count and the CRC32 of its results; dispatch_table_cases.bin holds one hash byte per case
+# (the low byte of the CRC32 of that case's results, slices in the table's order, zlib-compressed), which is what lets a mismatch name the first case that differs.  A knob set is crossed with the side whose code reads
+# it (FA_FWD_NW / FA_PACK_GQA: forward; the FA_BWD_* knobs: backward; FA_STRICT / FA_VARLEN_LIST: both); the forward-only features (return_softmax, a paged cache,
+# num_splits) have no backward parameter.
+_DT_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispatch_table.txt")
+_DT_CASES_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dispatch_table_cases.bin")
+_DT_B = (1, 8, 32)   # (B = 2 was dropped to keep the walk at about half a minute)
+_DT_S = ((1, 4096), (16, 2048), (128, 128), (128, 8192), (300, 300), (512, 384), (512, 768), (1024, 1024), (1536, 1536), (2048, 2048), (4096, 4096), (16384, 16384), (131072, 131072))
+_DT_H = ((4, 4), (16, 16), (32, 8), (32, 2), (128, 1), (6, 2))
+_DT_D = ((32, 0), (64, 0), (72, 0), (96, 0), (128, 0), (160, 0), (192, 0), (256, 0), (192, 128), (576, 512))
+_DT_MASKS = ((0, -1, -1), (1, -1, -1), (0, 1024, 0), (0, -1, 100), (0, 256, 256))   # (is_causal, window_left, window_right)
+_DT_FEATURES = (("none", {}), ("softcap", dict(softcap=30.0)), ("alibi", dict(alibi_slopes=1)), ("dropout", dict(p_dropout=0.1)),
+                ("dropout_randval", dict(p_dropout=0.1, randval=1)), ("softcap_alibi", dict(softcap=30.0, alibi_slopes=1)),
+                ("paged256", dict(block_table=1, page_block_size=256)), ("paged256_softcap", dict(block_table=1, page_block_size=256, softcap=30.0)),
+                ("num_splits1", dict(num_splits=1)), ("num_splits4", dict(num_splits=4)))
+_DT_BWD_FEATURES = ("none", "softcap", "alibi", "dropout", "softcap_alibi")
+_DT_KNOBS = (("default", {}, "fb"), ("strict", {"FA_STRICT": "1"}, "fb"), ("varlen_list0", {"FA_VARLEN_LIST": "0"}, "fb"), ("pack_gqa0", {"FA_PACK_GQA": "0"}, "f")) + \
+    tuple((f"fwd_nw{n}", {"FA_FWD_NW": str(n)}, "f") for n in (4, 8, 16, 34, 38, 64)) + tuple((f"bwd_mode{n}", {"FA_BWD_MODE": str(n)}, "b") for n in (-1, 3, 5)) + \
+    (("bwd_dq_nw64", {"FA_BWD_DQ_NW": "64"}, "b"), ("bwd_dkdv8", {"FA_BWD_DKDV": "8"}, "b"), ("bwd_gsplit0", {"FA_BWD_GSPLIT": "0"}, "b"), ("bwd_gsplit4", {"FA_BWD_GSPLIT": "4"}, "b"),
+     ("bwd_ds_cap1024", {"FA_BWD_DS_CAP_MB": "1024"}, "b"), ("bwd_c5_cap128", {"FA_BWD_C5_CAP_MB": "128"}, "b"))
+_DT_KNOB_NAMES = ("FA_STRICT", "FA_FWD_NW", "FA_PACK_GQA", "FA_VARLEN_LIST", "FA_BWD_MODE", "FA_BWD_DQ_NW", "FA_BWD_DKDV", "FA_BWD_GSPLIT", "FA_BWD_DS_CAP_MB", "FA_BWD_C5_CAP_MB",
+                  "FA_DKDV_PRESCALE", "FA_FZ_LINE")
+
+
+def _dt_slices():
+    for kname, env, sides in _DT_KNOBS:
+        for d in _DT_D:
+            for side in sides:
+                for fname, feat in _DT_FEATURES:
+                    if side == "b" and fname not in _DT_BWD_FEATURES:
+                        continue
+                    yield f"{'fwd' if side == 'f' else 'bwd'} {kname} d{d[0]}" + (f"_{d[1]}" if d[1] else "") + f" {fname}", side, env, d, feat
+
+
+def _dt_run(lib, side, d, feat, cases=None):
+    """(case count, results, one hash byte per case) of one slice, in grid order; `cases` (a list) also receives one (description, results) pair per case."""
+    import array
+    import zlib
+    res = array.array("q")
+    marks = bytearray()
+    fwd = side == "f"
+    a = _cabi.FaFwdParams() if fwd else _cabi.FaBwdParams()
+    D, Dv = d
+    a.d, a.d_v = D, Dv
+    a.softmax_scale = D ** -0.5
+    for k, v in feat.items():
+        setattr(a, k, v)
+    ref = C.byref(a)
+    out = (C.c_int32 * 8)()
+    sq, ws = lib.fa_fwd_schedule_query, lib.fa_fwd_workspace_bytes
+    dq, plan, bws = lib.fa_bwd_dq_schedule_query, lib.fa_bwd_plan_query, lib.fa_bwd_workspace_bytes
+    paged = "block_table" in feat
+    n = 0
+    for H, Hk in _DT_H:
+        for Sq, Sk in _DT_S:
+            a.h, a.h_k, a.seqlen_q, a.seqlen_k = H, Hk, Sq, Sk
+            a.q_row_stride, a.q_head_stride, a.q_batch_stride = H * D, D, Sq * H * D
+            a.k_row_stride, a.k_head_stride, a.k_batch_stride = Hk * D, D, (256 if paged else Sk) * Hk * D
+            vw = Dv or D
+            a.o_row_stride, a.o_head_stride, a.o_batch_stride = H * vw, vw, Sq * H * vw
+            a.v_row_stride, a.v_head_stride, a.v_batch_stride = Hk * vw, vw, (256 if paged else Sk) * Hk * vw
+            if not fwd:
+                a.do_row_stride, a.do_head_stride, a.do_batch_stride = a.o_row_stride, a.o_head_stride, a.o_batch_stride
+                a.dq_row_stride, a.dq_head_stride, a.dq_batch_stride = a.q_row_stride, a.q_head_stride, a.q_batch_stride
+                a.dk_row_stride, a.dk_head_stride, a.dk_batch_stride = a.k_row_stride, a.k_head_stride, a.k_batch_stride
+                a.dv_row_stride, a.dv_head_stride, a.dv_batch_stride = a.v_row_stride, a.v_head_stride, a.v_batch_stride
+            for B in _DT_B:
+                a.b = B
+                for causal, wl, wr in _DT_MASKS:
+                    a.is_causal, a.window_left, a.window_right = causal, wl, wr
+                    for packed in (0, 1, 4):   # fixed-length; a packed batch of B full sequences; a packed batch a quarter as long
+                        a.cu_seqlens_q = a.cu_seqlens_k = 1 if packed else None   # (the queries read the pointers as flags)
+                        a.total_q = B * Sq // max(packed, 1)
+                        if not fwd:
+                            a.total_k = B * Sk // max(packed, 1)
+                        mark = len(res)
+                        for dtype in (0, 1):
+                            a.dtype = dtype
+                            if fwd:
+                                res.extend((sq(ref, 0), sq(ref, 1), ws(ref)))
+                            else:
+                                rc = plan(ref, out, 8)
+                                res.extend((dq(ref), rc))
+                                res.extend(out if rc == 8 else (0,) * 8)
+                                res.append(bws(ref))
+                        if fwd:
+                            a.dtype = 2   # e4m3: the workspace query alone knows it
+                            res.append(ws(ref))
+                        n += 1
+                        marks.append(zlib.crc32(res[mark:].tobytes()) & 0xFF)
+                        if cases is not None:
+                            cases.append((f"B={B} Sq={Sq} Sk={Sk} H={H} Hk={Hk} d={D} d_v={Dv} causal={causal} window=({wl}, {wr}) packed={packed} total_q={a.total_q} {feat}",
+                                          list(res[mark:])))
+    return n, res, marks
+
+
+@contextlib.contextmanager
+def _dt_knobs(lib, env):
+    """The library's knobs read from `env` alone; the caller's environment is put back, whatever happens inside."""
+    saved = {k: os.environ.pop(k, None) for k in _DT_KNOB_NAMES}
+    try:
+        os.environ.update(env)
+        lib.fa_knobs_reload()
+        yield
+    finally:
+        for k in _DT_KNOB_NAMES:
+            os.environ.pop(k, None)
+        os.environ.update({k: v for k, v in saved.items() if v is not None})
+        lib.fa_knobs_reload()
+
+
+def _dt_table(lib):
+    """{slice name: (cases, crc32, hash byte per case)}, each slice under its knobs."""
+    import zlib
+    table = {}
+    for name, side, env, d, feat in _dt_slices():
+        with _dt_knobs(lib, env):
+            n, res, marks = _dt_run(lib, side, d, feat)
+        table[name] = (n, zlib.crc32(res.tobytes()), bytes(marks))
+    return table
+
+
+def test_dispatch_table_matches_the_recorded_one():
+    """fa_fwd_schedule_query (both varlen values), fa_fwd_workspace_bytes, fa_bwd_dq_schedule_query, fa_bwd_plan_query (all 8 words) and fa_bwd_workspace_bytes over the
+    grid above give what the recorded library gave.  A slice that differs is named with both checksums, and the first case of it whose hash byte differs from the
+    recorded one is printed in full, with what the library answers now."""
+    import zlib
+    lib = _cabi.load()
+    want, order = {}, []
+    with open(_DT_FILE) as f:
+        for line in f:
+            if line.strip() and not line.startswith("#"):
+                name, n, crc = line.rstrip("\n").rsplit(" ", 2)
+                want[name] = (int(n), int(crc, 16))
+                order.append(name)
+    got = _dt_table(lib)
+    assert sorted(got) == sorted(want), "the table's slices are not the generator's: " + str(sorted(set(got) ^ set(want))[:5])
+    bad = [s for s in order if got[s][:2] != want[s]]
+    if bad:
+        with open(_DT_CASES_FILE, "rb") as f:
+            recorded = zlib.decompress(f.read())
+        start = sum(want[s][0] for s in order[:order.index(bad[0])])
+        was, now = recorded[start:start + want[bad[0]][0]], got[bad[0]][2]
+        first = next((i for i, (x, y) in enumerate(zip(was, now)) if x != y), None)
+        name, side, env, d, feat = next(s for s in _dt_slices() if s[0] == bad[0])
+        cases = []
+        with _dt_knobs(lib, env):
+            _dt_run(lib, side, d, feat, cases)
+        print(f"{len(bad)} of {len(got)} slices differ; the first: '{name}' (cases, crc32) recorded {want[name][0]}, {want[name][1]:08x}, now {got[name][0]}, {got[name][1]:08x}")
+        if first is None:   # (equal hash bytes, one chance in 256 per differing case, or another case count)
+            print("no case's hash byte differs; its first case:", cases[0][0], "->", cases[0][1])
+        else:
+            print(f"its first differing case (number {first}):", cases[first][0], "-> now", cases[first][1])
+    assert not bad, bad[:10]
+
+
+if __name__ == "__main__":
+    import sys   # (run with PYTHONPATH=flash-attention_amd)
+    L = _cabi.load()
+    if sys.argv[1:2] == ["--record"]:
+        import zlib
+        table = _dt_table(L)
+        with open(_DT_FILE, "w") as f:
+            f.write("# slice (side, knob set, head dims, feature), cases, crc32 of the results -- recorded by tests/test_dispatch_cpu.py --record; see there\n")
+            for name, (n, crc, _) in table.items():
+                f.write(f"{name} {n} {crc:08x}\n")
+        with open(_DT_CASES_FILE, "wb") as f:
+            f.write(zlib.compress(b"".join(m for _, _, m in table.values()), 9))
+    elif sys.argv[1:2] == ["--dump"]:
+        name, side, env, d, feat = next(s for s in _dt_slices() if s[0] == sys.argv[2])
+        cases = []
+        with _dt_knobs(L, env):
+            _dt_run(L, side, d, feat, cases)
+        for desc, r in cases:
+            print(desc, "->", r)

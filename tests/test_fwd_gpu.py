@@ -406,3 +406,96 @@ def test_w64_softcap_varlen_and_default_dispatch(be, knobs):
     assert be.last_schedule()["fwd_kernel"] == 1
     be.fwd(q4, k4, v4, None, None, 0.1, 128 ** -0.5, True, -1, -1, 30.0, False, None)
     assert be.last_schedule()["fwd_kernel"] == 1
+
+
+# ---- a launch does what its query said (fa_api.cpp: both read one plan, fa_plan.h plan_fwd) ----
+_QUERY_CODE = {64: (3, 4), 34: (2, 4), 38: (2, 8), 4: (1, 4), 8: (1, 8), 16: (1, 16)}   # fa_fwd_schedule_query's code -> (LastSchedule fwd_kernel, fwd_nw)
+
+
+def _query_params(q, k, v, causal=False, window=(-1, -1), softcap=0.0, cu=None, max_q=0, max_k=0, num_splits=0):
+    """The FaFwdParams the binders fill for these tensors, as far as the queries read them (o has q's layout)."""
+    from flash_attn_amd import _cabi
+    a = _cabi.FaFwdParams()
+    a.q, a.k, a.v, a.o = q.data_ptr(), k.data_ptr(), v.data_ptr(), q.data_ptr()
+    if cu is None:
+        B, Sq, H, D = q.shape
+        Sk, Hk = k.shape[1], k.shape[2]
+        a.q_batch_stride, a.k_batch_stride, a.v_batch_stride, a.o_batch_stride = q.stride(0), k.stride(0), v.stride(0), q.stride(0)
+        a.seqlen_q, a.seqlen_k, a.total_q = Sq, Sk, B * Sq
+    else:
+        B, (_, H, D), Hk = cu.numel() - 1, q.shape, k.shape[1]
+        a.cu_seqlens_q = a.cu_seqlens_k = cu.data_ptr()
+        a.seqlen_q, a.seqlen_k, a.total_q = max_q, max_k, q.shape[0]
+    a.q_row_stride, a.q_head_stride = a.o_row_stride, a.o_head_stride = q.stride(-3), q.stride(-2)
+    a.k_row_stride, a.k_head_stride, a.v_row_stride, a.v_head_stride = k.stride(-3), k.stride(-2), v.stride(-3), v.stride(-2)
+    a.b, a.h, a.h_k, a.d, a.dtype = B, H, Hk, D, 1 if q.dtype == torch.bfloat16 else 0
+    a.is_causal, a.window_left, a.window_right = int(causal), window[0], window[1]
+    a.softmax_scale, a.softcap, a.num_splits = D ** -0.5, softcap, num_splits
+    return a
+
+
+@pytest.mark.parametrize("shape,causal,softcap,want,pack", [((8, 512, 512, 16, 16, 128), True, 0.0, 64, 1), ((2, 300, 300, 4, 4, 128), False, 0.0, 34, 1),
+                                                            ((2, 300, 300, 4, 4, 128), False, 30.0, 4, 1), ((2, 300, 300, 4, 4, 96), False, 0.0, 4, 1),
+                                                            ((2, 16, 2048, 32, 8, 128), False, 0.0, 4, 4)],
+                         ids=["w64", "pipelined", "softcap_lockstep", "d96_lockstep", "packed"])
+def test_fwd_launch_runs_the_schedule_its_query_names(be, shape, causal, softcap, want, pack):
+    import ctypes as C
+    from flash_attn_amd import _cabi
+    from oracle import attention_oracle as orc
+    B, Sq, Sk, H, Hk, D = shape
+    torch.manual_seed(31)
+    q = torch.randn(B, Sq, H, D, device="cuda", dtype=torch.bfloat16)
+    k = torch.randn(B, Sk, Hk, D, device="cuda", dtype=torch.bfloat16)
+    v = torch.randn_like(k)
+    code = _cabi.load().fa_fwd_schedule_query(C.byref(_query_params(q, k, v, causal, softcap=softcap)), 0)
+    assert code == want
+    out, lse = _fwd(be, q, k, v, causal, softcap=softcap)
+    s = be.last_schedule()
+    assert (s["fwd_kernel"], s["fwd_nw"]) == _QUERY_CODE[code] and s["fwd_pack"] == pack, (code, s)
+    if softcap > 0.0:   # (attention_torch has no softcap: the fp64 oracle, with the bound of test_fwd_packs_grouped_heads_of_short_query_chunks)
+        ref, _ = orc.attention_fwd(q, k, v, D ** -0.5, causal, (-1, -1), softcap)
+        assert float((out.float().cpu() - torch.from_numpy(ref).float()).abs().max()) < 2e-2
+    else:               # (the rule of test_forward_vs_fp32_reference)
+        ref32 = attention_torch(q.float(), k.float(), v.float(), causal, (-1, -1), upcast=True)[0]
+        pt, _ = attention_torch(q, k, v, causal, (-1, -1), upcast=False, reorder=True)
+        assert max_abs(out.float(), ref32) <= 2 * max_abs(pt.float(), ref32) + 1e-5
+
+
+def test_kvcache_splits_exactly_when_the_workspace_query_asks_for_partials(be):
+    import ctypes as C
+    from flash_attn_amd import _cabi
+    B, cap, H, D = 1, 4096, 8, 128
+    torch.manual_seed(32)
+    q = torch.randn(B, 1, H, D, device="cuda", dtype=torch.bfloat16)
+    kc, vc = torch.randn(B, cap, H, D, device="cuda", dtype=torch.bfloat16), torch.randn(B, cap, H, D, device="cuda", dtype=torch.bfloat16)
+    lens = torch.full((B,), cap, dtype=torch.int32, device="cuda")
+    run = lambda ns: be.fwd_kvcache(q, kc, vc, None, None, lens, None, None, None, None, None, None, None, D ** -0.5, False, -1, -1, 0.0, False, ns)[0]
+    ws = _cabi.load().fa_fwd_workspace_bytes(C.byref(_query_params(q, kc, vc)))
+    out = run(0)
+    assert (be.last_schedule()["fwd_splits"] > 1) == (ws > 0) and ws > 0, (ws, be.last_schedule())
+    out1 = run(1)
+    assert be.last_schedule()["fwd_splits"] == 1 and _cabi.load().fa_fwd_workspace_bytes(C.byref(_query_params(q, kc, vc, num_splits=1))) == 0
+    ref32 = attention_torch(q.float(), kc.float(), vc.float(), upcast=True)[0]
+    pt, _ = attention_torch(q, kc, vc, upcast=False, reorder=True)
+    for o in (out, out1):
+        assert max_abs(o.float(), ref32) <= 2 * max_abs(pt.float(), ref32) + 1e-5
+
+
+def test_varlen_work_list_runs_exactly_when_the_workspace_query_asks_for_one(be):
+    """The uneven packed batch of tests/test_kernel_census_gpu.py _run_schedule: fifteen sequences of 37 rows and one of 512."""
+    import ctypes as C
+    from flash_attn_amd import _cabi
+    torch.manual_seed(13)
+    lens = [37] * 7 + [512] + [37] * 8
+    cu = torch.tensor([0] + list(np.cumsum(lens)), dtype=torch.int32, device="cuda")
+    q = torch.randn(sum(lens), 4, 64, device="cuda", dtype=torch.bfloat16)
+    k, v = torch.randn(sum(lens), 2, 64, device="cuda", dtype=torch.bfloat16), torch.randn(sum(lens), 2, 64, device="cuda", dtype=torch.bfloat16)
+    a = _query_params(q, k, v, True, cu=cu, max_q=max(lens), max_k=max(lens))
+    ws, code = _cabi.load().fa_fwd_workspace_bytes(C.byref(a)), _cabi.load().fa_fwd_schedule_query(C.byref(a), 1)
+    out, lse = be.varlen_fwd(q, k, v, None, cu, cu, None, None, None, None, max(lens), max(lens), 0.0, 0.125, False, True, -1, -1, 0.0, False, None)[:2]
+    s = be.last_schedule()
+    assert (s["fwd_list"] == 1) == (ws > 0) and ws > 0 and (s["fwd_kernel"], s["fwd_nw"]) == _QUERY_CODE[code], (ws, code, s)
+    for b in (0, 7):   # (the bound of test_varlen_default_schedule_matches_per_sequence_within_rounding)
+        s0, s1 = int(cu[b]), int(cu[b + 1])
+        o1, l1 = _fwd(be, q[None, s0:s1], k[None, s0:s1], v[None, s0:s1], True)
+        assert max_abs(out[s0:s1].float(), o1[0].float()) < 1.6e-2 and max_abs(lse[:, s0:s1], l1[0]) < 1e-4
